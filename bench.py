@@ -10,6 +10,12 @@ that traffic when offload is off, both directions:
             frames corrupted) -> per-frame pass/fail status (ip.cc:121-127, tcp.hh:876-883)
 value = bytes checksummed by all ranks / max-over-ranks wall time, GiB/s.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what that figure
+needs: it builds the batches, warms up, times the N steps and prints the line
+(--dump-outputs DIR also writes the last timed step's results as .npy).  With
+--full it also checks the results (a warm-up run of its own, the timed run's
+outputs against it), measures the HBM read ceiling and runs the CPU baseline.
+
 Multi-GPU: one process per GPU, each with its own independent shard (weak
 scaling, no data-path collective; the only collectives are the timing
 barrier and the max-over-ranks reduction, on gloo).  Under torchrun the ranks
@@ -75,8 +81,19 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--packets", type=int, default=1 << 20, help="frames per GPU")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the pre-timing parity check (A/B builds only)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="skip the parity checks (udp1500: those of --full; A/B builds only)")
+    ap.add_argument("--full", action="store_true",
+                    help="udp1500 (the metric's config): besides the headline's timed steps, also check the results "
+                         "(a warm-up run of its own before the timed one, the timed run's outputs against it), "
+                         "measure the HBM read ceiling and run the CPU baseline.  A plain run sets up, warms up, "
+                         "times the steps and prints the line.  The other configs (--config) are asked for by "
+                         "name and run in full either way")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="udp1500: after the timed steps, write what the last timed step computed, as a caller "
+                         "receives it, to DIR/<name>.npy (float32): tx_checksums (n x 2: IPv4 header, UDP), "
+                         "rx_status (n), and rx_checksums with --rx-out2; ranks past 0 write <name>.rank<r>.npy.  "
+                         "The inputs depend on the arguments alone, so two builds compare output for output")
     ap.add_argument("--pmc", default=None, help="PMC summary JSON for roofline.traffic (default: newest for the config)")
     ap.add_argument("--rotate", type=int, default=4,
                     help="distinct batches (pairs for udp1500) launched in turn, so no launch replays cached lines")
@@ -672,6 +689,25 @@ def emit(metric, value, unit, args, world, wall, dtype, config, roof=None, cpu=N
     print(json.dumps(d), flush=True)
 
 
+def dump_outputs(path: str, rank: int, **arrays) -> None:
+    """--dump-outputs: each result array of the last timed step as
+    DIR/<name>.npy in float32 (16-bit checksums and status bytes are exact in
+    it; int16 storage read as the u16 it holds).  At most 64 MB in all: the
+    headline's arrays are 12 MB per rank and written whole; of a larger
+    array (--packets) a fixed, seeded sample of rows, in order."""
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    budget = (64 << 20) // len(arrays)  # bytes of float32 per array
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:
+            a = a.view(np.uint16)
+        rows = budget // (4 * max(1, a[0].size))
+        if a.shape[0] > rows:
+            a = a[np.sort(np.random.default_rng(SEED).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a.astype(np.float32))
+
+
 def read_ceiling(data, nbytes, stream, reps=10):
     """Measured HBM read ceiling: the plain nt stream over the same bytes."""
     sink = torch.zeros(native.load().sccsum_read_probe_blocks(), dtype=torch.int64, device=data.device)
@@ -760,23 +796,26 @@ def run_udp1500(args, world, rank, dev):
             batch.ipv4_frames(rxs[r], out2=outs[r][1], status=sts[r], stream=s)
 
     torch.cuda.synchronize()  # the batches were built on the default stream
-    if begin:
-        begin()
-    for k in range(warm):
-        step(k)
-    if end:
-        end()
-    LAUNCHES.add(kern, 1 if engine else per_step * warm)
-    torch.cuda.synchronize()
-    # sanity: every uncorrupted rx frame verifies, every corrupted one fails; the tx outputs match the generate pass
-    for st_rx in sts:
-        n_fail = int(((st_rx & 2) == 0).sum())
-        assert args.no_check or n_fail == bad.numel(), f"verify failures {n_fail} != corrupted {bad.numel()}"
-    # the warm-up's results per rotation; the timed run's are checked against them afterwards (VERDICT r05:
-    # the timed region itself was never checked), its outputs poisoned first so that a step that never ran
-    # shows: 0xFFFF is no IPv4 or UDP checksum of these frames (~fold(sum) is 0xFFFF only for a zero sum)
-    want_tx = [o[0].clone() for o in outs]
-    want_st = [s.clone() for s in sts]
+    check = args.full and not args.no_check
+    if args.full:  # a warm-up run of its own, whose results the checks read (a plain run has timed()'s alone)
+        if begin:
+            begin()
+        for k in range(warm):
+            step(k)
+        if end:
+            end()
+        LAUNCHES.add(kern, 1 if engine else per_step * warm)
+        torch.cuda.synchronize()
+    if check:
+        # sanity: every uncorrupted rx frame verifies, every corrupted one fails; the tx outputs match the generate pass
+        for st_rx in sts:
+            n_fail = int(((st_rx & 2) == 0).sum())
+            assert n_fail == bad.numel(), f"verify failures {n_fail} != corrupted {bad.numel()}"
+        # the warm-up's results per rotation; the timed run's are checked against them afterwards (VERDICT r05:
+        # the timed region itself was never checked), its outputs poisoned first so that a step that never ran
+        # shows: 0xFFFF is no IPv4 or UDP checksum of these frames (~fold(sum) is 0xFFFF only for a zero sum)
+        want_tx = [o[0].clone() for o in outs]
+        want_st = [s.clone() for s in sts]
     ran = sorted({k % R for k in range(warm, warm + args.steps)})
 
     def poison():
@@ -789,13 +828,17 @@ def run_udp1500(args, world, rank, dev):
     # the warm-up again, right before the timed region: the checks above leave the GPU idle for
     # milliseconds, and a run that starts cold pays for it (+50 us after a 20 ms gap, +175 us after
     # 100 ms: profiles/r06_run_cost.log)
-    wall, step_s = timed(step, args.steps, warm, world, streams, begin, end, between=None if args.no_check else poison)
+    wall, step_s = timed(step, args.steps, warm, world, streams, begin, end, between=poison if check else None)
     LAUNCHES.add(kern, 1 if engine else per_step * args.steps)
     avg_launch_s = step_s / per_step
     stream = streams[0]
     if engine:
         eng.close()  # raises if the run left a published step undone (sccsum_engine_destroy)
-    if not args.no_check:  # outside the timed region
+    if args.dump_outputs:  # what the last timed step's caller holds: its rotation's result buffers
+        last = (warm + args.steps - 1) % R
+        dump_outputs(args.dump_outputs, rank, tx_checksums=outs[last][0].view(n, 2), rx_status=sts[last],
+                     **({"rx_checksums": outs[last][1].view(n, 2)} if (args.rx_out2 or not (multi or engine)) else {}))
+    if check:  # outside the timed region
         torch.cuda.synchronize()
         for r in ran:
             n_fail = int(((sts[r] & 2) == 0).sum())
@@ -811,11 +854,11 @@ def run_udp1500(args, world, rank, dev):
     roof_alg, roof_s = alg, avg_launch_s
     if engine:  # the launch is the run: every step's bytes over the run's time (the same ratio)
         roof_alg, roof_s = alg * args.steps, avg_launch_s * args.steps
-    ceiling = read_ceiling(txs[0].data, txs[0].bytes_len, stream)
+    ceiling = read_ceiling(txs[0].data, txs[0].bytes_len, stream) if args.full else None  # (a run of its own)
     ranks = per_rank(world, rank, dev, **rank_rate(2 * n * FRAME, args.steps), avg_launch_us=avg_launch_s * 1e6,
                      read_ceiling_GBps=ceiling, frac=alg / avg_launch_s / 1e9 / HBM_PEAK_GBPS, launch=args.launch)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(txs[0], args.cpu_seconds)
     if rank == 0:
         emit(METRIC, value, "GiB/s", args, world, wall, "u8",
@@ -827,7 +870,7 @@ def run_udp1500(args, world, rank, dev):
                                f"batches submitted into it as one step, at most {args.engine_in_flight} steps in flight" if engine
                                else "one sccsum_ipv4_frames launch per batch (2 per step)")),
               "rotation": f"{R} distinct tx/rx batch pairs launched in turn ({2 * R * n * FRAME / 1e9:.1f} GB per GPU)",
-              "timed_run_checked": (None if args.no_check else
+              "timed_run_checked": (None if not check else
                                     "after the timed region: every rotation's rx status and tx checksums equal the "
                                     "warm-up's (outputs poisoned before it), failures == corrupted frames"
                                     + ("; the run waited on its last step and its engine closed clean" if engine
@@ -838,7 +881,8 @@ def run_udp1500(args, world, rank, dev):
                       kern + (" (sccsum_ipv4_frames_multi, tx + rx)" if multi else
                               (" (sccsum_engine_*, tx + rx per step; one launch = the timed run)" if engine
                                else " (sccsum_ipv4_frames)")), sel, args,
-                      {"measured_read_ceiling_GBps": round(ceiling, 1)}), cpu, extra={"per_rank": ranks})
+                      {"measured_read_ceiling_GBps": round(ceiling, 1)} if args.full else None), cpu,
+             extra={"per_rank": ranks})
 
 
 def run_tcp64k(args, world, rank, dev):
@@ -1440,6 +1484,8 @@ def main():
     global SYNC_MODE, SHARE_DEVICES
     SYNC_MODE = args.sync
     SHARE_DEVICES = args.share_devices
+    if args.dump_outputs and (args.config != "udp1500" or args.dry_run):
+        sys.exit("bench.py: --dump-outputs writes the headline's outputs (--config udp1500, no --dry-run)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     _imports()

@@ -121,3 +121,26 @@ def test_layout_traffic_of_aligned_frames():
     assert abs(d["traffic_ratio"] - (alg + gap) / alg) < 1e-5
     assert abs(d["frac_of_streamed_bytes"] - 0.749 * (alg + gap) / alg) < 1e-4
     assert bench.layout_traffic(alg, 0, packets, 0.8)["traffic_ratio"] == 1.0  # packed: no gaps
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: int16 storage is written as the u16 it holds, in
+    float32; an array past its share of the 64 MB cap is cut to a fixed,
+    seeded sample of rows in order; ranks past 0 write <name>.rank<r>.npy."""
+    bench = _bench()
+    bench._imports()
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda *a: None)  # CPU tensors here
+    out2 = torch.tensor([[-1, 0], [0x1234, -32768]], dtype=torch.int16)
+    st = torch.tensor([3, 1], dtype=torch.uint8)
+    bench.dump_outputs(str(tmp_path), 0, tx_checksums=out2, rx_status=st)
+    a, b = np.load(tmp_path / "tx_checksums.npy"), np.load(tmp_path / "rx_status.npy")
+    assert a.dtype == np.float32 and a.tolist() == [[65535.0, 0.0], [4660.0, 32768.0]]
+    assert b.dtype == np.float32 and b.tolist() == [3.0, 1.0]
+    rows = (64 << 20) // 4 + 1000  # one array: more float32 rows than 64 MB holds
+    big = (torch.arange(rows, dtype=torch.int32) % 251).to(torch.uint8)
+    for _ in range(2):  # the same sample every time
+        bench.dump_outputs(str(tmp_path), 1, rx_status=big)
+        s = np.load(tmp_path / "rx_status.rank1.npy")
+        assert s.nbytes == 64 << 20 and s.dtype == np.float32
+        idx = np.sort(np.random.default_rng(bench.SEED).choice(rows, (64 << 20) // 4, replace=False))
+        assert np.array_equal(s, big.numpy()[idx].astype(np.float32))

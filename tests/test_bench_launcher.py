@@ -90,8 +90,8 @@ def test_launcher_reports_a_failed_rank_and_stops_the_others():
 def test_launcher_two_ranks_on_the_gpu():
     """Two rank processes on the box's one GPU (a rehearsal of the driver's
     --gpus N run: each rank builds, checks and times its own shard)."""
-    d = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--packets", "65536", "--rotate", "1", "--no-cpu",
-               "--share-devices", timeout=300)
+    d = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--packets", "65536", "--rotate", "1", "--full",
+               "--no-cpu", "--share-devices", timeout=300)
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert d["config"]["global_batch"] == 2 * 65536
     pr = d["per_rank"]
@@ -155,7 +155,7 @@ def test_torchrun_two_ranks_on_the_gpu():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "1", "--packets", "65536", "--rotate", "1",
-                        "--no-cpu", "--share-devices"], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
+                        "--full", "--no-cpu", "--share-devices"], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["value"] > 0
@@ -189,3 +189,44 @@ def test_e2e_two_ranks_report_per_rank_pcie():
                "--share-devices", timeout=400)
     check_e2e_line(d, 2)
     print(json.dumps(d["ranks_summary"]))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(dev, tmp_path):
+    """A plain run (no --full) times its steps and prints the line without the
+    checks, the read ceiling or the CPU baseline; --dump-outputs writes what
+    the last timed step computed (rotation (warm + steps - 1) % R, warm =
+    max(warmup, R)), here compared with the oracle on the same seeded inputs
+    rebuilt in this process."""
+    import numpy as np
+    import oracle
+    import torch
+
+    import bench
+    from seastar_amd import devsynth
+
+    n, steps, warmup, R = 4096, 3, 1, 2
+    d = _bench("--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--packets", str(n), "--rotate", str(R),
+               "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == steps and d["warmup"] == warmup and d["value"] > 0 and d["unit"] == "GiB/s"
+    assert d["ms_per_step"] > 0 and abs(d["ms_per_step"] - d["per_rank"][0]["ms_per_step"]) < 1e-3
+    assert abs(d["value"] - 2 * n * bench.FRAME / (d["ms_per_step"] * 1e-3) / 2**30) <= 0.01 * d["value"]
+    assert d["cpu_baseline"] is None and d["config"]["timed_run_checked"] is None
+    assert "measured_read_ceiling_GBps" not in d["roofline"] and d["per_rank"][0]["read_ceiling_GBps"] is None
+    assert sorted(os.listdir(tmp_path / "out")) == ["rx_status.npy", "tx_checksums.npy"]
+    got_tx, got_st = np.load(tmp_path / "out" / "tx_checksums.npy"), np.load(tmp_path / "out" / "rx_status.npy")
+    assert got_tx.dtype == np.float32 and got_tx.shape == (n, 2) and got_st.dtype == np.float32 and got_st.shape == (n,)
+
+    r = (max(warmup, R) + steps - 1) % R
+    tx = devsynth.udp_frames(n, bench.FRAME, seed=bench.SEED + 104723 * r, device=dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(bench.SEED)
+    bad = torch.randperm(n, device=dev, generator=g)[: n // 100]
+    off, length = tx.off.cpu().numpy().astype(np.uint64), tx.length.cpu().numpy().astype(np.uint32)
+    want_tx, _ = oracle.batch_ipv4(tx.data.cpu().numpy(), off, length)
+    assert np.array_equal(got_tx, want_tx.astype(np.float32))
+    rx = devsynth.store_checksums(tx, torch.from_numpy(want_tx.view(np.int16).reshape(-1)).to(dev))
+    devsynth.corrupt(rx, bad, byte=700)
+    _, want_st = oracle.batch_ipv4(rx.data.cpu().numpy(), off, length)
+    assert np.array_equal(got_st, want_st.astype(np.float32))
+    assert int(((want_st & 2) == 0).sum()) == n // 100  # the corrupted frames, and only they, fail the UDP check

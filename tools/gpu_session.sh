@@ -6,8 +6,8 @@
 # the first failure, time limit or fault ends the session):
 #   pytest                 the GPU test suite (-m gpu), one process
 #   smoke                  __graft_entry__.smoke()
-#   headline               bench.py as the driver runs it (N=1, CPU baseline included)
-#   bench:CFG[+ARG...]     bench.py --config CFG --steps 20 --no-cpu ARG...   (ARGs joined by '+')
+#   headline               bench.py --full (N=1; results checked, read ceiling and CPU baseline included)
+#   bench:CFG[+ARG...]     bench.py --config CFG --steps 20 --full --no-cpu ARG...   (ARGs joined by '+')
 #   trace:CFG[+ARG...]     rocprofv3 --kernel-trace --stats of the bench command
 #   prof:CFG[+ARG...]      trace + separate FETCH_SIZE and WRITE_SIZE passes of the bench command,
 #                          cut to the timed dispatches by tools/prof_timed.py ($TAG_pmc_CFG.json)
@@ -52,10 +52,10 @@ run_step() {
         smoke)
             timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > "$O/smoke.log" 2>&1 ;;
         headline)
-            timeout -k 10 400 python bench.py > "$O/bench_headline.log" 2>&1 ;;
+            timeout -k 10 400 python bench.py --full > "$O/bench_headline.log" 2>&1 ;;
         bench)
             split "$rest"
-            timeout -k 10 400 python bench.py --config "$CFG" --steps 20 --no-cpu "${ARGS[@]}" \
+            timeout -k 10 400 python bench.py --config "$CFG" --steps 20 --full --no-cpu "${ARGS[@]}" \
                 >> "$O/bench_$n$LIBTAG.log" 2>&1 ;;
         lib)
             if [ "$rest" = default ]; then
