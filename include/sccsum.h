@@ -21,6 +21,14 @@
  *                             L4 pseudo-header + segment  include/seastar/net/tcp.hh:876-883 }
  *   sccsum_fragments    N x checksummer::sum(const packet&)  src/net/ip_checksum.cc:64-68
  *                       (fragment lists with the odd-byte carry) + get()
+ *   sccsum_ipv4_fill    the tx writers, in place on contiguous frames:
+ *                       csum.sum(p); write_nbo_checksum  include/seastar/net/tcp.hh:1691-1694,
+ *                       src/net/udp.cc:184-195, ipv4::send  src/net/ip.cc:266-278,
+ *                       icmp::received  src/net/ip.cc:464-474
+ *   sccsum_ipv4_fill_desc  the same on packets given as fragment lists, written
+ *                       where the fragments lie (a tx packet: header fragment
+ *                       + payload fragments); sccsum_burst_set_fill makes it
+ *                       the burst queue's batch step (qp::poll_tx)
  *   sccsum_*_multi      the above for up to 16 batches (rx queues) in one launch
  *   sccsum_pseudo_seed  ipv4_traits::{tcp,udp}_pseudo_header_checksum
  *                       include/seastar/net/ip.hh:70-75 (host arithmetic, O(1))
@@ -96,7 +104,8 @@ extern "C" {
  * any number of threads may submit into one engine, sccsum_engine_create_opts
  * (idle and dependency limits), SCCSUM_EFAULT; the desc calls accept a NULL
  * descriptor array when no packet has fragments; sccsum_engine_stop / _destroy
- * report SCCSUM_EIDLE only when a published step was left undone. */
+ * report SCCSUM_EIDLE only when a published step was left undone.
+ * 4, additive (round 7): sccsum_ipv4_fill_desc, sccsum_burst_set_fill. */
 #define SCCSUM_ABI_VERSION 4
 
 #define SCCSUM_OK 0
@@ -527,6 +536,19 @@ int sccsum_burst_submit_mapped(sccsum_burst* b, const sccsum_fragment* frags, ui
  * the next poll / drain launches it again. */
 int sccsum_burst_poll(sccsum_burst* b, int* did_work);
 
+/* Tx form of a SCCSUM_PIPE_IPV4 queue: while fill_mode (sccsum_ipv4_fill's
+ * mode bits and rules) is set, every batch is ONE sccsum_ipv4_fill_desc launch
+ * on the fragments where they lie, whatever sccsum_set_burst_fused says: at
+ * a packet's completion its fragments hold the generated checksums (wire-ready
+ * mbufs: the hook for qp::poll_tx, net.cc:81-105), and the callback gets the
+ * values stored and the fill status bits.  The fragments are WRITTEN, so only
+ * sccsum_burst_submit_mapped takes packets (sccsum_burst_submit, whose bytes
+ * are copies, returns SCCSUM_EINVAL), they must be writable by the device, and
+ * no two fragments of a batch may overlap.  fill_mode 0 returns to values
+ * only.  SCCSUM_EINVAL: a SCCSUM_PIPE_SPANS queue or a bad mode; SCCSUM_EBUSY:
+ * a packet is staged or a batch in flight (drain first). */
+int sccsum_burst_set_fill(sccsum_burst* b, uint32_t fill_mode);
+
 /* Launch what is staged, wait for every batch in flight, deliver them all. */
 int sccsum_burst_drain(sccsum_burst* b);
 
@@ -573,6 +595,28 @@ int sccsum_spans_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first,
 int sccsum_ipv4_frames_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                             const uint32_t* d_len, const void* d_stage, uint16_t* d_out2, uint8_t* d_status,
                             uint64_t n, uint32_t max_len, void* stream);
+
+/* sccsum_ipv4_fill on fragment lists: GENERATE the checksums of n IPv4 packets
+ * given as for sccsum_ipv4_frames_desc and STORE them where the fragments lie
+ * — the call WRITES through desc.src (through d_stage + dst_off for a fragment
+ * with src == NULL), so that memory is device memory or pinned / registered
+ * host memory the device can write; over PCIe the bytes are visible to the
+ * host once `stream` is synchronised.  One kernel, one wave per packet: it
+ * decodes the header (which may be split), sums with every field counted as
+ * zero — what the fields held does not matter — and stores at most six bytes
+ * itself (IP +10/+11, the L4 field, an echo reply's type and code); a field's
+ * two bytes may lie in different fragments.  mode, its validity, the fields,
+ * the frames that are skipped, d_out2 and d_status (each may be NULL) are
+ * exactly sccsum_ipv4_fill's; FILL_IP alone and FILL_L4_PSEUDO (| FILL_TSO)
+ * read only header bytes, and FILL_L4 / FILL_ICMP_ECHO read the payload only
+ * of packets whose field they write.  A packet whose fragments do not tile it
+ * is not written: values 0, status SCCSUM_ST_RANGE.  No two fragments of a
+ * batch may overlap.  The mode is checked first (SCCSUM_EINVAL), then n == 0
+ * is SCCSUM_OK; pointer / alignment errors and a stream of another device are
+ * SCCSUM_EINVAL before any device work. */
+int sccsum_ipv4_fill_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
+                          const uint32_t* d_len, void* d_stage, uint16_t* d_out2, uint8_t* d_status,
+                          uint64_t n, uint32_t max_len, uint32_t mode, void* stream);
 
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);

@@ -15,6 +15,8 @@
 //   the same, stored into the frames (wire-ready tx)          ipv4_fill(batch, SCCSUM_FILL_IP | SCCSUM_FILL_L4, ...)
 //   checksummer::sum(const packet&)  ip_checksum.cc:64-68     spans_desc / ipv4_frames_desc (fragments
 //                                                             anywhere the device reads); C-ABI sccsum_fragments
+//   tx packets (header fragment + payload fragments), filled   ipv4_fill_desc(...) / burst_queue::set_fill (the
+//       where they lie: tcp.hh:1691-1694, udp.cc:184-195          qp::poll_tx hook: wire-ready mbufs at completion)
 //   toeplitz_hash(rss_key(), forward_hash)  net.cc:330-341    ipv4_rss(batch, key, ...) / ipv4_frames_rss(...)
 //   per packet as qp::poll_tx / DPDK rx hand them over         burst_queue (host packets, async completion)
 //       net.cc:81-105, dpdk.cc:2190-2204
@@ -155,6 +157,19 @@ public:
               "sccsum_ipv4_frames_desc");
     }
 
+    // ipv4_fill on fragment lists: generate and store the checksums where the
+    // fragments lie — the memory behind d_desc[].src (d_stage for src ==
+    // nullptr) is WRITTEN: device memory or pinned / registered host memory,
+    // visible to the host once `stream` is synchronised.  mode: SCCSUM_FILL_*;
+    // d_out2 and d_status may be null.  A field may straddle two fragments.
+    void ipv4_fill_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
+                        const uint32_t* d_len, uint64_t n, uint32_t max_len, uint32_t mode, void* d_stage,
+                        uint16_t* d_out2, uint8_t* d_status, void* stream) const {
+        check(sccsum_ipv4_fill_desc(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len, mode,
+                                    stream),
+              "sccsum_ipv4_fill_desc");
+    }
+
     void sync(void* stream) const { check(sccsum_sync(stream), "sccsum_sync"); }
 };
 
@@ -206,6 +221,18 @@ public:
         const int rc = sccsum_burst_submit_mapped(_q, frags, nfrag, seed, ticket);
         if (rc == SCCSUM_EBUSY) return false;
         check(rc, "sccsum_burst_submit_mapped");
+        return true;
+    }
+    // tx form (SCCSUM_PIPE_IPV4 queues): while a fill mode (SCCSUM_FILL_*) is
+    // set, each batch generates its packets' checksums and stores them in the
+    // mapped fragments themselves — at completion the mbufs are wire-ready,
+    // `done` gets the values stored and the fill status bits, and submit()
+    // (whose bytes are copies) throws.  0 = values only.  false: a packet is
+    // staged or in flight (drain, then set again).
+    bool set_fill(uint32_t mode) {
+        const int rc = sccsum_burst_set_fill(_q, mode);
+        if (rc == SCCSUM_EBUSY) return false;
+        check(rc, "sccsum_burst_set_fill");
         return true;
     }
     bool poll() {

@@ -409,6 +409,35 @@ def ipv4_frames_desc(desc: torch.Tensor, first: torch.Tensor, off: torch.Tensor,
     return out2[: 2 * n].view(n, 2) if n else out2[:0].view(0, 2)
 
 
+def ipv4_fill_desc(desc: torch.Tensor, first: torch.Tensor, off: torch.Tensor, length: torch.Tensor, max_len: int,
+                   mode: int = native.FILL_IP | native.FILL_L4, stage: torch.Tensor | None = None,
+                   out2: torch.Tensor | None = None, status: torch.Tensor | None = None,
+                   stream=None) -> torch.Tensor:
+    """sccsum_ipv4_fill_desc: generate the checksums of frames given as
+    fragment lists and store them where the fragments lie (the memory behind
+    the descriptors, or `stage`, is written).  Returns the values stored,
+    [n, 2] int16 (IP, L4; 0 where nothing was stored)."""
+    lib = native.load()
+    name = "sccsum_ipv4_fill_desc"
+    n = int(off.numel())
+    dev = off.device
+    if int(first.numel()) != n + 1 or first.dtype != torch.int32 or (desc is not None and desc.dtype != torch.uint8):
+        raise ValueError(f"{name}: first must be int32 [n + 1] and desc uint8 records (or None: no fragments)")
+    _need(off, n, torch.int64, "off", dev)
+    _need(length, n, torch.int32, "length", dev)
+    _need(first, n + 1, torch.int32, "first", dev)
+    _need(desc, 0, torch.uint8, "desc", dev)
+    _need(stage, 0, torch.uint8, "stage", dev)
+    _need(out2, 2 * n, torch.int16, "out2", dev)
+    _need(status, n, torch.uint8, "status", dev)
+    if out2 is None:
+        out2 = _scratch(max(2 * n, 2), dev, stream, torch.int16)
+    native.check(lib.sccsum_ipv4_fill_desc(_ptr(desc), ctypes_ptr(first), ctypes_ptr(off), ctypes_ptr(length),
+                                           _ptr(stage), ctypes_ptr(out2), _ptr(status), n, max_len, mode,
+                                           _stream(stream)), name)
+    return out2[: 2 * n].view(n, 2) if n else out2[:0].view(0, 2)
+
+
 def read_probe(buf: torch.Tensor, nbytes: int, sink: torch.Tensor | None = None, stream=None) -> torch.Tensor:
     """Stream-read nbytes of buf with the kernels' load shape (HBM ceiling probe)."""
     lib = native.load()

@@ -87,6 +87,15 @@ class BurstQueue:
             self._held[ticket.value] = bufs
         return ticket.value
 
+    def set_fill(self, mode: int) -> None:
+        """sccsum_burst_set_fill: while `mode` (native.FILL_*) is set, every
+        batch generates its packets' checksums and stores them in the mapped
+        fragments themselves (the tx form: submit with mapped=True only);
+        results / status are the values stored and the fill status bits.
+        0 = values only again.  Raises SccsumError(SCCSUM_EBUSY) while a packet
+        is staged or in flight."""
+        native.check(self._lib.sccsum_burst_set_fill(self._h, mode), "sccsum_burst_set_fill")
+
     def poll(self) -> bool:
         did = ctypes.c_int()
         native.check(self._lib.sccsum_burst_poll(self._h, ctypes.byref(did)), "sccsum_burst_poll")

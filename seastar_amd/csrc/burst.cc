@@ -71,6 +71,7 @@ struct sccsum_burst {
     };
     int device = 0;
     int mode = SCCSUM_PIPE_SPANS;
+    uint32_t fill = 0;  // sccsum_burst_set_fill: the SCCSUM_FILL_* mode, 0 = values only
     uint64_t batch_bytes = 0;
     uint32_t batch_packets = 0;
     uint64_t max_delay_ns = 0;
@@ -143,10 +144,14 @@ int launch_slot_ops(sccsum_burst* b, sccsum_burst::Slot& s);
 // (on separate streams they share PCIe and finish together, leaving the GPU
 // idle while the host refills).  Batches with copies keep their slot's stream
 // so one batch's copies overlap another's kernel.
-bool one_launch(const sccsum_burst::Slot& s) { return s.mapped && t_fused == 2; }
+// A fill queue (sccsum_burst_set_fill) holds zero-copy packets only and writes
+// their fields where they lie: always the one-launch form.
+bool one_launch(const sccsum_burst* b, const sccsum_burst::Slot& s) {
+    return b->fill != 0 || (s.mapped && t_fused == 2);
+}
 
 hipStream_t stream_of(const sccsum_burst* b, const sccsum_burst::Slot& s) {
-    return one_launch(s) ? b->slots[0].stream : s.stream;
+    return one_launch(b, s) ? b->slots[0].stream : s.stream;
 }
 
 int launch_slot(sccsum_burst* b, sccsum_burst::Slot& s) {
@@ -161,17 +166,20 @@ int launch_slot_ops(sccsum_burst* b, sccsum_burst::Slot& s) {
     const hipStream_t st = stream_of(b, s);
     const uint64_t n = s.npk;
     const bool spans = b->mode != SCCSUM_PIPE_IPV4;
-    if (one_launch(s)) {
+    if (one_launch(b, s)) {
         // zero-copy batch: the kernel reads the pinned metadata, descriptors
         // and (for copied packets) staged bytes over PCIe and writes the
         // results into the pinned result block the callback reads
         s.h_first[n] = s.ndesc;
         auto* h_out = reinterpret_cast<uint16_t*>(s.h_res);
         uint8_t* h_status = s.h_res + 2 * width(b) * n;
-        const int rk = spans ? sccsum_spans_desc(s.h_desc, s.h_first, s.h_off, s.h_len, s.h_seed, s.h_stage, h_out,
-                                                 h_status, n, s.max_len, st)
-                             : sccsum_ipv4_frames_desc(s.h_desc, s.h_first, s.h_off, s.h_len, s.h_stage, h_out,
-                                                       h_status, n, s.max_len, st);
+        const int rk =
+            spans    ? sccsum_spans_desc(s.h_desc, s.h_first, s.h_off, s.h_len, s.h_seed, s.h_stage, h_out, h_status, n,
+                                         s.max_len, st)
+            : b->fill ? sccsum_ipv4_fill_desc(s.h_desc, s.h_first, s.h_off, s.h_len, s.h_stage, h_out, h_status, n,
+                                              s.max_len, b->fill, st)
+                      : sccsum_ipv4_frames_desc(s.h_desc, s.h_first, s.h_off, s.h_len, s.h_stage, h_out, h_status, n,
+                                                s.max_len, st);
         if (rk != SCCSUM_OK) return rk;
         SCCSUM_TRY(hipEventRecord(s.done, st));
         s.st = sccsum_burst::state::inflight;
@@ -322,6 +330,7 @@ int sccsum_burst_create(int device, int mode, uint64_t batch_bytes, uint32_t bat
 static int submit(sccsum_burst* b, const sccsum_fragment* frags, uint32_t nfrag, uint32_t seed, uint64_t* ticket,
                   bool mapped) {
     if (!b || (nfrag && !frags)) return SCCSUM_EINVAL;
+    if (b->fill && !mapped) return SCCSUM_EINVAL;  // a fill writes the packet itself, not a staged copy
     uint64_t L = 0;
     uint32_t nd = 0;
     for (uint32_t j = 0; j < nfrag; ++j) {
@@ -385,6 +394,25 @@ int sccsum_burst_submit(sccsum_burst* b, const sccsum_fragment* frags, uint32_t 
 int sccsum_burst_submit_mapped(sccsum_burst* b, const sccsum_fragment* frags, uint32_t nfrag, uint32_t seed,
                                uint64_t* ticket) {
     return submit(b, frags, nfrag, seed, ticket, true);
+}
+
+int sccsum_burst_set_fill(sccsum_burst* b, uint32_t fill_mode) {
+    if (!b || b->mode != SCCSUM_PIPE_IPV4) return SCCSUM_EINVAL;
+    // the mode rules are sccsum_ipv4_fill_desc's (an empty batch checks the mode only)
+    if (fill_mode != 0 &&
+        sccsum_ipv4_fill_desc(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, fill_mode, nullptr) !=
+            SCCSUM_OK) {
+        return SCCSUM_EINVAL;
+    }
+    if (b->in_callback || b->inflight) return SCCSUM_EBUSY;
+    if (b->open != SIZE_MAX) {
+        auto& s = b->slots[b->open];
+        if (s.npk) return SCCSUM_EBUSY;
+        s.st = sccsum_burst::state::free;  // opened, nothing staged
+        b->open = SIZE_MAX;
+    }
+    b->fill = fill_mode;
+    return SCCSUM_OK;
 }
 
 int sccsum_burst_poll(sccsum_burst* b, int* did_work) {

@@ -3158,12 +3158,31 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const sccsum_gather_desc
 // lane in flight; a one-fragment packet takes the contiguous-span path.  A fragment's bytes are summed at their address parity and the
 // fragment's folded sum byte-swapped when its address and its packet offset
 // differ in parity (the odd carry of the reference's fragment loop).
-template <int U, bool IPV4>
+//
+// FILL (frames only; flags = the SCCSUM_FILL_* mode): generate and store in
+// place, the tx form (tcp.hh:1691-1694, udp.cc:184-195, ip.cc:266-278,
+// ip.cc:464-474 over a fragment list).  Same validation and header decode;
+// every sum leaves its own field out (the IP sum bytes 10-11, the L4 sum the
+// TCP / UDP field, an echo request's sum its type, code and checksum bytes:
+// the bytes are masked while summing, so an all-zero message keeps the
+// reference's zero), so what the fields held does not matter.  The payload is
+// read only when a sum over it is stored (FILL_L4 on a TCP / UDP frame that
+// gets its field, FILL_ICMP_ECHO on an echo request).  The wave then stores
+// at most six bytes itself, one per lane; each lane picks up its byte's
+// address as the fragment loop passes over it (a field's two bytes may lie in
+// different fragments: walking the descriptors again after the sum cost two
+// more dependent round trips per packet); the skip rules are fill_apply's.
+// Every stored value depends on the wave's loads, the stored bytes are left
+// out of the wave's own sums, and no wave waits for another.  One-fragment
+// packets take the general path here (one more round trip than
+// span_packet's; DESIGN.md "Fill on fragment lists").
+template <int U, bool IPV4, bool FILL = false>
 __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
     const sccsum_gather_desc* __restrict__ desc, const uint32_t* __restrict__ first,
     const uint64_t* __restrict__ off, const uint32_t* __restrict__ len, const uint32_t* __restrict__ seed,
     const uint8_t* __restrict__ stage, uint16_t* __restrict__ out, uint8_t* __restrict__ status, uint64_t n,
     uint32_t flags) {
+    static_assert(!FILL || IPV4, "in-place generate is a frames mode");
     const bool raw = !IPV4 && (flags & kFlagRaw);
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -3227,7 +3246,7 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
             if (bad || (IPV4 && L < 20)) {
                 if (lane == 0) {
                     if (IPV4) {
-                        reinterpret_cast<uint32_t*>(out)[p] = 0;
+                        if (!FILL || out) reinterpret_cast<uint32_t*>(out)[p] = 0;
                     } else {
                         out[p] = 0;
                     }
@@ -3236,9 +3255,28 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
                 continue;
             }
 
+            // FILL: the address of packet byte `pos` (< L), from whichever fragment holds it
+            [[maybe_unused]] auto locate = [&](uint32_t pos) -> uintptr_t {
+                uint32_t at = 0;
+                for (uint32_t j = f0; j < f1; ++j) {
+                    const sccsum_gather_desc d = desc[j];
+                    if (pos < at + d.len) return frag_addr(d) + (pos - at);
+                    at += d.len;
+                }
+                return 0;
+            };
             uint32_t S = 0, ipc = 0, pseudo = 0;
             uint8_t st = 0;
-            if (f1 - f0 <= 1) {
+            // FILL: which fields this packet gets (wave-uniform) and the packet
+            // bytes [xl, xh) its L4 sum leaves out
+            [[maybe_unused]] bool put_l4 = false, echo = false;
+            [[maybe_unused]] uint32_t l4_off = 0, l4_fo = 0, xl = 0, xh = 0;
+            // FILL, per lane: the packet byte lane k < 6 stores, whether it does, and
+            // that byte's address, picked up as the fragment loop passes over it
+            [[maybe_unused]] uint32_t spos = 0;
+            [[maybe_unused]] bool son = false;
+            [[maybe_unused]] uintptr_t saddr = 0;
+            if (!FILL && f1 - f0 <= 1) {
                 // one fragment (or an empty packet): the contiguous-span path, header
                 // and first units in one round trip
                 const uint8_t* ptr = L ? reinterpret_cast<const uint8_t*>(frag_addr(d0)) : stage;
@@ -3271,12 +3309,57 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
                                static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hb), 4 * k + 2)) << 16 |
                                static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hb), 4 * k + 3)) << 24;
                     }
-                    const FrameHeader F = frame_header(h[0], h[1], h[2], h[3], h[4], L);
-                    ipc = F.ipc;
-                    st = F.st;
-                    pseudo = F.pseudo;
-                    rs = F.l4_off;
-                    re = F.l4_off + F.l4_len;
+                    if constexpr (FILL) {
+                        const FrameDecode D = frame_decode(h[0], h[1], h[2], h[3], h[4], L);
+                        st = static_cast<uint8_t>(D.st);
+                        l4_off = D.l4_off;
+                        if (flags & SCCSUM_FILL_IP) {
+                            ipc = ~fold16(static_cast<uint64_t>(h[0]) + h[1] + (h[2] & 0xffffu) + h[3] + h[4]) & 0xffffu;
+                            st |= SCCSUM_ST_OK;
+                        }
+                        // as fill_apply: malformed, an IP fragment, or ihl < 5 -> no L4 write
+                        const bool atomic = (D.st & (SCCSUM_ST_MALFORMED | SCCSUM_ST_IPFRAG)) == 0u && D.ihl >= 5u;
+                        l4_fo = D.proto == 17u ? 6u : (D.proto == 6u ? 16u : 0u);
+                        put_l4 = (flags & (SCCSUM_FILL_L4 | SCCSUM_FILL_L4_PSEUDO)) != 0u && l4_fo != 0u && atomic &&
+                                 D.l4_len >= l4_fo + 2u;
+                        if ((flags & SCCSUM_FILL_ICMP_ECHO) && D.proto == 1u && atomic && D.l4_len >= 8u) {
+                            uint32_t type = 0;
+                            if (lane == 0) type = *gld(reinterpret_cast<const uint8_t*>(locate(l4_off)));
+                            echo = __builtin_amdgcn_readfirstlane(type) == 8u;  // echo_request (ip.cc:469)
+                        }
+                        if (flags & SCCSUM_FILL_L4_PSEUDO) {
+                            // the partial a NIC completes: the folded pseudo-header (TSO: TCP length 0)
+                            pseudo = ((flags & SCCSUM_FILL_TSO) && D.proto == 6u)
+                                         ? fold16(static_cast<uint64_t>(h[3] & 0xffffu) + (h[3] >> 16) +
+                                                  (h[4] & 0xffffu) + (h[4] >> 16) + (D.proto << 8))
+                                         : D.pseudo;
+                        } else {
+                            pseudo = D.pseudo;  // 0 for ICMP
+                        }
+                        const bool sum = echo || (put_l4 && (flags & SCCSUM_FILL_L4));
+                        rs = sum ? l4_off : 0u;
+                        re = sum ? l4_off + D.l4_len : 0u;
+                        xl = l4_off + (echo ? 0u : l4_fo);
+                        xh = xl + (echo ? 4u : 2u);
+                        // lanes 0-1 the IP field, 2-3 the L4 field, 4-5 an echo reply's type and code
+                        if (lane < 2u) {
+                            son = (flags & SCCSUM_FILL_IP) != 0u;
+                            spos = 10u + lane;
+                        } else if (lane < 4u) {
+                            son = put_l4 || echo;
+                            spos = l4_off + (echo ? 2u : l4_fo) + (lane - 2u);
+                        } else if (lane < 6u) {
+                            son = echo;
+                            spos = l4_off + (lane - 4u);
+                        }
+                    } else {
+                        const FrameHeader F = frame_header(h[0], h[1], h[2], h[3], h[4], L);
+                        ipc = F.ipc;
+                        st = F.st;
+                        pseudo = F.pseudo;
+                        rs = F.l4_off;
+                        re = F.l4_off + F.l4_len;
+                    }
                 }
                 uint64_t acc = 0;  // per lane: folded fragment partials, each at its packet parity
                 uint32_t at = 0;   // packet offset of fragment j
@@ -3284,6 +3367,9 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
                     const sccsum_gather_desc d = desc[j];
                     const uint32_t lo = rs > at ? rs : at;
                     const uint32_t hi = re < at + d.len ? re : at + d.len;
+                    if constexpr (FILL) {  // (spos < at wraps past any length)
+                        if (spos - at < d.len) saddr = frag_addr(d) + (spos - at);
+                    }
                     if (lo < hi) {
                         const uintptr_t A = frag_addr(d);
                         const uint32_t head = static_cast<uint32_t>(A & 15u);
@@ -3300,10 +3386,35 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
                                 const uint32_t c = g + static_cast<uint32_t>(u * kWave) + lane;
                                 v[u] = c < c1 ? load_unit(a0 + 16u * c) : u32x4{0, 0, 0, 0};
                             }
+                            if constexpr (FILL) {
+                                // [xl, xh) relative to a0, like ulo / uhi; only a group that holds
+                                // some of those bytes pays for the second mask (the byte masks are
+                                // most of this kernel's ALU work: with both on every unit the
+                                // HBM-resident fill ran 1.3x the verify)
+                                const int el = static_cast<int>(head + xl) - static_cast<int>(at);
+                                const int eh = static_cast<int>(head + xh) - static_cast<int>(at);
+                                const int g16 = 16 * static_cast<int>(g);
+                                const bool cut = el < uhi && eh > ulo && el < g16 + 16 * U * kWave && eh > g16;
+                                if (cut) {
     #pragma unroll
-                            for (int u = 0; u < U; ++u) {
-                                const int c16 = 16 * static_cast<int>(g + u * kWave + lane);
-                                part += unit_sum(v[u], ulo - c16, uhi - c16);
+                                    for (int u = 0; u < U; ++u) {
+                                        const int c16 = 16 * static_cast<int>(g + u * kWave + lane);
+                                        part += unit_sum(v[u], ulo - c16, min(uhi, el) - c16) +
+                                                unit_sum(v[u], max(ulo, eh) - c16, uhi - c16);
+                                    }
+                                } else {
+    #pragma unroll
+                                    for (int u = 0; u < U; ++u) {
+                                        const int c16 = 16 * static_cast<int>(g + u * kWave + lane);
+                                        part += unit_sum(v[u], ulo - c16, uhi - c16);
+                                    }
+                                }
+                            } else {
+    #pragma unroll
+                                for (int u = 0; u < U; ++u) {
+                                    const int c16 = 16 * static_cast<int>(g + u * kWave + lane);
+                                    part += unit_sum(v[u], ulo - c16, uhi - c16);
+                                }
                             }
                         }
                         uint32_t f = fold16(part);
@@ -3315,6 +3426,24 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
                 S = fold16(wave_sum(fold16(acc)));
             }
 
+            if constexpr (FILL) {
+                // r = the L4 value stored (0 when none is), then the stores
+                uint32_t r = 0;
+                if (flags & SCCSUM_FILL_L4_PSEUDO) {
+                    if (put_l4) r = pseudo;
+                } else if (put_l4 || echo) {
+                    r = ~fold16(static_cast<uint64_t>(S) + pseudo) & 0xffffu;
+                }
+                const uint32_t val = (lane < 2u ? ipc : (lane < 4u ? r : 0u)) >> (8u * (lane & 1u));
+#ifndef SCCSUM_AB_FILL_DESC_NOSTORE  // (A/B only: generate without the field stores, to see what they cost)
+                if (son && saddr) *gst(reinterpret_cast<uint8_t*>(saddr)) = static_cast<uint8_t>(val);
+#endif
+                if (lane == 0) {
+                    if (out) reinterpret_cast<uint32_t*>(out)[p] = ipc | r << 16;
+                    if (status) status[p] = static_cast<uint8_t>(st | ((put_l4 || echo) ? SCCSUM_ST_L4_OK : 0u));
+                }
+                continue;
+            }
             if (IPV4) {
                 S = fold16(static_cast<uint64_t>(S) + pseudo);
             } else if (seed && !raw) {
@@ -3361,6 +3490,46 @@ int launch_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const
         case 1: return go(csum_desc_kernel<1, IPV4>);
         case 2: return go(csum_desc_kernel<2, IPV4>);
         default: return go(csum_desc_kernel<4, IPV4>);
+    }
+}
+
+// sccsum_ipv4_fill's mode rules (sccsum.h): at least one bit, only known bits,
+// FILL_L4_PSEUDO excludes FILL_L4 and FILL_ICMP_ECHO, FILL_TSO needs FILL_L4_PSEUDO.
+bool fill_mode_ok(uint32_t mode) {
+    constexpr uint32_t kAll =
+        SCCSUM_FILL_IP | SCCSUM_FILL_L4 | SCCSUM_FILL_L4_PSEUDO | SCCSUM_FILL_TSO | SCCSUM_FILL_ICMP_ECHO;
+    return mode != 0 && !(mode & ~kAll) && !((mode & SCCSUM_FILL_L4) && (mode & SCCSUM_FILL_L4_PSEUDO)) &&
+           !((mode & SCCSUM_FILL_TSO) && !(mode & SCCSUM_FILL_L4_PSEUDO)) &&
+           !((mode & SCCSUM_FILL_ICMP_ECHO) && (mode & SCCSUM_FILL_L4_PSEUDO));
+}
+
+// The fill form of launch_desc: one launch, the kernel stores the fields
+// through the descriptors' own addresses (d_stage for src == NULL fragments).
+int launch_desc_fill(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
+                     const uint32_t* d_len, void* d_stage, uint16_t* d_out2, uint8_t* d_status, uint64_t n,
+                     uint32_t max_len, uint32_t mode, void* stream) {
+    if (!fill_mode_ok(mode)) return SCCSUM_EINVAL;
+    if (n == 0) return SCCSUM_OK;
+    if (!d_first || !d_off || !d_len || (reinterpret_cast<uintptr_t>(d_desc) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_first) & 3u) || (reinterpret_cast<uintptr_t>(d_off) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_len) & 3u) || (reinterpret_cast<uintptr_t>(d_out2) & 3u)) {
+        return SCCSUM_EINVAL;
+    }
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    int dev = 0;
+    if (const int rc = launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const auto* st = static_cast<const uint8_t*>(d_stage);
+    const dim3 g(grid_for(n, dev));
+    auto go = [&](auto kern) {
+        return static_cast<int>(launch_kernel(kern, g, s, d_desc, d_first, d_off, d_len,
+                                              static_cast<const uint32_t*>(nullptr), st, d_out2, d_status, n, mode));
+    };
+    // the header-only modes read no payload: one unit per lane is plenty
+    const bool sums = (mode & (SCCSUM_FILL_L4 | SCCSUM_FILL_ICMP_ECHO)) != 0;
+    switch (sums ? units_class(max_len) : 1) {
+        case 1: return go(csum_desc_kernel<1, true, true>);
+        case 2: return go(csum_desc_kernel<2, true, true>);
+        default: return go(csum_desc_kernel<4, true, true>);
     }
 }
 
@@ -4073,6 +4242,13 @@ int sccsum_ipv4_frames_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_
                                      stream);
 }
 
+int sccsum_ipv4_fill_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
+                          const uint32_t* d_len, void* d_stage, uint16_t* d_out2, uint8_t* d_status, uint64_t n,
+                          uint32_t max_len, uint32_t mode, void* stream) {
+    return sccsum::launch_desc_fill(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len, mode,
+                                    stream);
+}
+
 uint64_t sccsum_fragments_workspace(uint64_t nfrag) { return ((2 * nfrag + 15) & ~uint64_t(15)) + nfrag + 16; }
 
 int sccsum_fragments(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_frag_off, const uint32_t* d_frag_len,
@@ -4102,13 +4278,7 @@ int sccsum_fragments(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_
 int sccsum_ipv4_fill(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
                      uint16_t* d_out2, uint8_t* d_status, uint64_t n, uint32_t max_len, uint32_t mode,
                      void* stream) {
-    constexpr uint32_t kAll =
-        SCCSUM_FILL_IP | SCCSUM_FILL_L4 | SCCSUM_FILL_L4_PSEUDO | SCCSUM_FILL_TSO | SCCSUM_FILL_ICMP_ECHO;
-    if (mode == 0 || (mode & ~kAll) || ((mode & SCCSUM_FILL_L4) && (mode & SCCSUM_FILL_L4_PSEUDO)) ||
-        ((mode & SCCSUM_FILL_TSO) && !(mode & SCCSUM_FILL_L4_PSEUDO)) ||
-        ((mode & SCCSUM_FILL_ICMP_ECHO) && (mode & SCCSUM_FILL_L4_PSEUDO))) {
-        return SCCSUM_EINVAL;
-    }
+    if (!sccsum::fill_mode_ok(mode)) return SCCSUM_EINVAL;
     if (n == 0) return SCCSUM_OK;
     const bool two_pass = (mode & (SCCSUM_FILL_L4 | SCCSUM_FILL_ICMP_ECHO)) != 0;
     if (two_pass ? !sccsum::batch_ok<true>(d_bytes, d_off, d_len, nullptr, d_out2, d_status, sccsum::kFlagFillL4)

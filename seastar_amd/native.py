@@ -95,6 +95,8 @@ _PROTOS = {
     "sccsum_gather": (ctypes.c_int, [_vp, _u64, _vp, _vp]),
     "sccsum_spans_desc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp]),
     "sccsum_ipv4_frames_desc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp]),
+    "sccsum_ipv4_fill_desc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "sccsum_burst_set_fill": (ctypes.c_int, [_vp, _u32]),
     "sccsum_set_burst_fused": (ctypes.c_int, [ctypes.c_int]),
     "sccsum_burst_poll": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "sccsum_burst_drain": (ctypes.c_int, [_vp]),
