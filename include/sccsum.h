@@ -163,7 +163,14 @@ uint32_t sccsum_pseudo_seed(uint32_t src_host, uint32_t dst_host, uint8_t proto,
  *                 from seed d_seed[i] (d_seed may be NULL: no seed).
  *   d_status[i] = SCCSUM_ST_OK if d_out[i] == 0 (verify); may be NULL.
  *   max_len     = upper bound of d_len[] used to pick the kernel variant
- *                 (0 = unknown; any value is correct, it only tunes speed). */
+ *                 (0 = unknown; any value is correct, it only tunes speed).
+ * Every uint64_t d_off[i] and every uint32_t d_len[i] is either summed
+ * exactly or refused with SCCSUM_ST_RANGE: the range test is d_off > bytes_len
+ * || d_len > bytes_len - d_off in 64 bits (an offset whose low 32 bits, or
+ * whose wrapped end, would be in range is refused), and a span of 2^31 bytes
+ * or more, up to 2^32 - 1, sums like any other (one wave scans it).  The same
+ * holds for every entry point that takes d_off / d_len, in buffers wider than
+ * 4 GiB too (tests/test_gpu_wide.py). */
 int sccsum_spans(const void* d_bytes, uint64_t bytes_len,
                  const uint64_t* d_off, const uint32_t* d_len, const uint32_t* d_seed,
                  uint16_t* d_out, uint8_t* d_status, uint64_t n, uint32_t max_len,
@@ -588,7 +595,12 @@ int sccsum_gather(const sccsum_gather_desc* d_desc, uint64_t n, void* d_dst, voi
  * Results and status as sccsum_spans / sccsum_ipv4_frames (frames: IPv4
  * header + L4, the header may be split across fragments).  d_desc, d_first,
  * d_off, d_len, d_seed, d_out, d_status: device arrays (aligned to their
- * element size, d_desc to 8).  max_len: the longest packet (sizes the loop). */
+ * element size, d_desc to 8).  max_len: the longest packet (sizes the loop).
+ * Any d_off and any d_len value is either summed exactly or refused with
+ * SCCSUM_ST_RANGE: dst_off is compared with the 64-bit d_off (+ the bytes
+ * before the fragment), so a d_off past 2^32 whose low 32 bits equal dst_off
+ * does not tile; packet and fragment lengths up to 2^32 - 1 sum exactly, and
+ * src is a full 64-bit address. */
 int sccsum_spans_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                       const uint32_t* d_len, const uint32_t* d_seed, const void* d_stage, uint16_t* d_out,
                       uint8_t* d_status, uint64_t n, uint32_t max_len, void* stream);

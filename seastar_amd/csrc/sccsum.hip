@@ -215,12 +215,29 @@ struct PacketSum {
     uint8_t st;
 };
 
+// span_packet and the fragment loop of csum_desc_kernel carry byte ranges and
+// unit indices as int / uint32_t: a span (a fragment) of kWideLen bytes or
+// more goes to exact_range_sum, 64-bit throughout, so every uint32_t length
+// sums exactly and the common path's arithmetic never leaves [0, 2^31).
+constexpr uint32_t kWideLen = 1u << 30;
+__device__ uint32_t exact_range_sum(const uint8_t* a0, uint64_t rs, uint64_t re, uint32_t lane);
+
 template <int U, bool IPV4>
 __device__ __forceinline__ PacketSum span_packet(const uint8_t* ptr, uint32_t L, int lane) {
     const uintptr_t addr = reinterpret_cast<uintptr_t>(ptr);
     const int head = static_cast<int>(addr & 15u);
     const uint8_t* a0 = ptr - head;
-    const uint32_t nunits = L ? (static_cast<uint32_t>(head) + L + 15u) >> 4 : 0u;
+    if (!IPV4 && L >= kWideLen) {  // (L is wave-uniform)
+        PacketSum W{};
+        W.S = exact_range_sum(a0, static_cast<uint64_t>(head), static_cast<uint64_t>(head) + L,
+                              static_cast<uint32_t>(lane));
+        if (addr & 1u) W.S = swap16(W.S);
+        return W;
+    }
+    // a frame's summed bytes end at min(ip_len, L) <= 65 535, whatever L is:
+    // the units past them are never loaded (and head + L + 15 cannot wrap)
+    const uint32_t Lu = IPV4 && L > 65535u ? 65535u : L;
+    const uint32_t nunits = Lu ? (static_cast<uint32_t>(head) + Lu + 15u) >> 4 : 0u;
 
     // Frame mode: the 20-byte IPv4 header as 5 dwords re-aligned to the
     // packet start (lanes 0..5 load the covering dwords; lane 5 only when
@@ -3374,6 +3391,19 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
                         const uintptr_t A = frag_addr(d);
                         const uint32_t head = static_cast<uint32_t>(A & 15u);
                         const uint8_t* a0 = reinterpret_cast<const uint8_t*>(A - head);
+                        if (!IPV4 && hi - at >= kWideLen) {
+                            // a fragment's range past the int arithmetic below (spans only: a
+                            // frame's summed bytes lie in its first 65 595): 64-bit, one unit a lane
+                            uint32_t f = exact_range_sum(a0, static_cast<uint64_t>(head) + (lo - at),
+                                                         static_cast<uint64_t>(head) + (hi - at), lane);
+                            // (exact_range_sum returns the wave's total in every lane; acc is summed
+                            // over the wave again below)
+                            if (lane != 0) f = 0;
+                            if ((A ^ at) & 1u) f = swap16(f);
+                            acc += f;
+                            at += d.len;
+                            continue;
+                        }
                         // the summed bytes, relative to the aligned base a0
                         const int ulo = static_cast<int>(head + lo - at), uhi = static_cast<int>(head + hi - at);
                         const uint32_t c0 = static_cast<uint32_t>(ulo) >> 4;
