@@ -30,6 +30,13 @@
  *                       + payload fragments); sccsum_burst_set_fill makes it
  *                       the burst queue's batch step (qp::poll_tx)
  *   sccsum_*_multi      the above for up to 16 batches (rx queues) in one launch
+ *   sccsum_steer_run    N x device::hash2cpu / device::forward_dst
+ *                       include/seastar/net/net.hh:287-305 (dpdk hash2qid src/net/dpdk.cc:505-508)
+ *                       as interface::dispatch_packet src/net/net.cc:330-344 and
+ *                       ipv4::handle_received_packet src/net/ip.cc:197 call them, after the
+ *                       drops of src/net/ip.cc:121-144, plus the per-shard packet lists
+ *                       their forward() calls fill; sccsum_steer_build_reta =
+ *                       qp::build_sw_reta src/net/net.cc:214-231
  *   sccsum_pseudo_seed  ipv4_traits::{tcp,udp}_pseudo_header_checksum
  *                       include/seastar/net/ip.hh:70-75 (host arithmetic, O(1))
  *
@@ -105,7 +112,8 @@ extern "C" {
  * (idle and dependency limits), SCCSUM_EFAULT; the desc calls accept a NULL
  * descriptor array when no packet has fragments; sccsum_engine_stop / _destroy
  * report SCCSUM_EIDLE only when a published step was left undone.
- * 4, additive (round 7): sccsum_ipv4_fill_desc, sccsum_burst_set_fill. */
+ * 4, additive (round 7): sccsum_ipv4_fill_desc, sccsum_burst_set_fill.
+ * 4, additive (round 8): sccsum_steer_* (rx steering). */
 #define SCCSUM_ABI_VERSION 4
 
 #define SCCSUM_OK 0
@@ -391,7 +399,95 @@ int sccsum_ipv4_frames_rss(const void* d_bytes, uint64_t bytes_len, const uint64
                            uint16_t* d_out2, uint8_t* d_status, uint64_t n, uint32_t max_len, const uint8_t* key,
                            uint32_t key_len, int rss_mode, uint32_t* d_hash, void* stream);
 
-#define SCCSUM_FILL_IP        0x01u /* IPv4 header checksum, field at +10 (ip.cc:266-278) */
+/* ---- Rx steering: hash2cpu for a batch + its stable partition by shard ------
+ * What the rx path does with a packet's hash, for a whole batch on the device:
+ * device::forward_dst (net.hh:291-300) / device::hash2cpu (net.hh:301-305)
+ * give every packet its destination shard, and the batch's packet indices are
+ * grouped by shard in arrival order — the per-shard lists that
+ * interface::dispatch_packet's forward() (net.cc:330-344) and
+ * ipv4::handle_received_packet (ip.cc:197) build one packet at a time.  It
+ * consumes only the d_hash / d_status arrays the RSS and frames launches
+ * write, so it follows any launch form.
+ *
+ * sccsum_steer_map (all tables are HOST memory, read by sccsum_steer_create /
+ * sccsum_steer_dest only):
+ *   hash2qid(hash) = redir[hash & (redir_size - 1)] when redir_size != 0
+ *                    (dpdk.cc:505-508), else hash % hw_queues (net.hh:287-289)
+ *   forward_dst(q, hash) = sw_reta[q][(hash >> table_bits) % 128] when queue q
+ *                    has a _sw_reta, else q itself (a queue index past
+ *                    hw_queues is a proxy queue: it never has one)
+ *   SCCSUM_STEER_DISPATCH: dest = forward_dst(src_cpu, hash)
+ *   SCCSUM_STEER_HASH2CPU: dest = forward_dst(hash2qid(hash), hash)
+ * A hash of 0 (what the reference and the RSS kernels give a packet they
+ * cannot hash) steers like any other.
+ *
+ * sccsum_steer_create validates every table entry (redir < hw_queues, sw_reta
+ * < ncpu, a queue without a _sw_reta < ncpu since it maps to itself) and
+ * copies the tables to `device`; control plane: it allocates and
+ * synchronises, and leaves the calling thread's current device as it was.
+ * The object is immutable: any number of threads and streams may run it.
+ *
+ * sccsum_steer_run, packet i of n:
+ *   dropped when d_status is given and (d_status[i] & need) != need ||
+ *   (d_status[i] & reject) != 0 — the caller's policy, e.g. need =
+ *   SCCSUM_ST_OK, reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE for the
+ *   frames the reference drops before it steers (ip.cc:121-144); with
+ *   d_status NULL nothing is dropped and need / reject must be 0.
+ *   d_cpu[i]   = its shard, 0xFF when dropped; may be NULL.
+ *   d_first    = ncpu + 2 entries, required: d_order[d_first[c] ..
+ *                d_first[c + 1]) are shard c's packets, bucket c = ncpu the
+ *                dropped ones, d_first[ncpu + 1] = n.
+ *   d_order[n] = packet indices grouped by bucket ascending, ascending inside
+ *                a bucket (a STABLE partition: a flow's packets keep their
+ *                order); may be NULL: counts only, no scatter pass.
+ *   d_workspace: sccsum_steer_workspace(s, n) bytes of device scratch, 16-byte
+ *                aligned; d_hash, d_order, d_first 4-byte aligned.
+ *   Every output is a function of the inputs alone (no atomic decides a
+ *   position): two runs give identical bytes.
+ * Three small kernels on `stream` (count, scan, scatter; the scan is two past
+ * 31 shards), one chain of plain dependent launches, no allocation, no memset,
+ * no host synchronisation: capturable.  `stream` must belong to
+ * the object's device (NULL = the current device's null stream, which must be
+ * that device): SCCSUM_EINVAL otherwise.  n == 0 writes d_first (zeros) when
+ * it is given and is SCCSUM_OK without device work when it is NULL; n > 2^32-1
+ * is SCCSUM_EINVAL (indices are 32-bit), like every argument error before any
+ * device work.  DISPATCH from a src_cpu that has no _sw_reta sends every
+ * packet to src_cpu, which must then be < ncpu. */
+typedef struct sccsum_steer sccsum_steer;
+typedef struct sccsum_steer_map {
+    uint32_t ncpu;          /* destination shards 0..ncpu-1; 1..255 (0xFF marks a dropped packet) */
+    uint32_t hw_queues;     /* 1..256: device::hw_queues_count() */
+    uint32_t table_bits;    /* device::_rss_table_bits, 0..31 */
+    uint32_t redir_size;    /* 0, or a power of two 1..512: the dpdk _redir_table's size */
+    const uint8_t* redir;   /* redir_size entries < hw_queues; NULL iff redir_size == 0 */
+    const uint8_t* sw_reta; /* [hw_queues][128] entries < ncpu: row q = queue q's _sw_reta */
+    const uint8_t* sw_reta_set; /* [hw_queues] 0/1: queue q has a _sw_reta (its row is ignored when 0);
+                                   NULL = every queue has one */
+} sccsum_steer_map;
+
+#define SCCSUM_STEER_DISPATCH 0 /* forward_dst(src_cpu, hash): dispatch_packet, net.cc:330-344 */
+#define SCCSUM_STEER_HASH2CPU 1 /* forward_dst(hash2qid(hash), hash): ip.cc:197, tcp.hh:839 */
+
+int sccsum_steer_create(int device, const sccsum_steer_map* map, sccsum_steer** out);
+int sccsum_steer_destroy(sccsum_steer* s);
+uint64_t sccsum_steer_workspace(const sccsum_steer* s, uint64_t n);
+int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const uint32_t* d_hash,
+                     const uint8_t* d_status, uint32_t need, uint32_t reject, uint64_t n, uint8_t* d_cpu,
+                     uint32_t* d_order, uint32_t* d_first, void* d_workspace, void* stream);
+
+/* One hash through a map on the host (O(1), no table validation: the entries
+ * it reads are returned as they are); 0xFFFFFFFF for a NULL map, a bad scalar
+ * field or a bad mode. */
+uint32_t sccsum_steer_dest(const sccsum_steer_map* map, int mode, uint32_t src_cpu, uint32_t hash);
+
+/* qp::build_sw_reta (net.cc:214-231) with the same float arithmetic: the
+ * 128-entry table of n cpus (strictly ascending, as the reference's std::map
+ * iterates; each <= 254) with weights >= 0.  SCCSUM_EINVAL when the weights
+ * do not fill all 128 entries (their sum is 0), which the reference would
+ * leave unset. */
+int sccsum_steer_build_reta(const uint32_t* cpus, const float* weights, uint32_t n, uint8_t reta[128]);
+
+#define SCCSUM_FILL_IP       0x01u /* IPv4 header checksum, field at +10 (ip.cc:266-278) */
 #define SCCSUM_FILL_L4        0x02u /* full TCP/UDP checksum: pseudo-header + segment (udp.cc:190-192,
                                        tcp.hh:1691-1692 without tx offload) */
 #define SCCSUM_FILL_L4_PSEUDO 0x04u /* tx-offload partial: the folded pseudo-header alone, i.e. the

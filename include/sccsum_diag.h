@@ -107,6 +107,11 @@ int sccsum_read_probe_blocks(void);
  * (the two-pass form).  SCCSUM_EINVAL for anything else. */
 int sccsum_set_burst_fused(int on);
 
+/* Rx steering (sccsum_steer_run): the packets of one tile, i.e. of one block
+ * of its count and scatter kernels (a constant of the build; the edge-size
+ * tests are built around it). */
+int sccsum_steer_tile_packets(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,9 @@
 //   tx packets (header fragment + payload fragments), filled   ipv4_fill_desc(...) / burst_queue::set_fill (the
 //       where they lie: tcp.hh:1691-1694, udp.cc:184-195          qp::poll_tx hook: wire-ready mbufs at completion)
 //   toeplitz_hash(rss_key(), forward_hash)  net.cc:330-341    ipv4_rss(batch, key, ...) / ipv4_frames_rss(...)
-//   per packet as qp::poll_tx / DPDK rx hand them over         burst_queue (host packets, async completion)
+//   hash2cpu / forward_dst + forward()  net.hh:287-305,       rx_steering (shard of every packet + the batch's
+//       net.cc:330-344, ip.cc:197                                 indices grouped by shard, in arrival order)
+//   per packet as qp::poll_tx / DPDK rx hand them over        burst_queue (host packets, async completion)
 //       net.cc:81-105, dpdk.cc:2190-2204
 //   a shard's steady stream of bursts, polled like its queues  resident_engine (one grid, steps streamed in;
 //       reactor.cc:3543-3550                                   fills too: submit_fill)
@@ -316,6 +318,69 @@ public:
         check(sccsum_engine_wait(_e, step, timeout_ns), "sccsum_engine_wait");
     }
     void stop() { check(sccsum_engine_stop(_e), "sccsum_engine_stop"); }
+};
+
+// Rx steering (<sccsum.h> sccsum_steer_*): device::hash2cpu / forward_dst
+// (net.hh:287-305) for a whole rx batch, and the batch's packet indices
+// grouped by destination shard in arrival order — what dispatch_packet's
+// forward() (net.cc:330-344) builds one packet at a time.  Immutable after
+// construction: every shard of the GPU may run the same object on its own
+// stream.
+//   uint8_t reta[128];
+//   rx_steering::build_reta(cpus, weights, ncpu, reta);          // qp::build_sw_reta, net.cc:214-231
+//   sccsum_steer_map map = {ncpu, 1, 0, 0, nullptr, reta, nullptr};
+//   rx_steering steer(gpu, map);
+//   engine.ipv4_frames_rss(batch, key, key_len, SCCSUM_RSS_DISPATCH, nullptr, d_status, d_hash, stream);
+//   steer.run(SCCSUM_STEER_HASH2CPU, 0, d_hash, d_status, SCCSUM_ST_OK, SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE,
+//             batch.n, d_cpu, d_order, d_first, d_ws, stream);   // shard c: d_order[d_first[c] .. d_first[c+1])
+class rx_steering {
+    sccsum_steer* _s = nullptr;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // validates every table entry and copies the tables (host memory) to `device`
+    rx_steering(int device, const sccsum_steer_map& map) {
+        check(sccsum_steer_create(device, &map, &_s), "sccsum_steer_create");
+    }
+    rx_steering(const rx_steering&) = delete;
+    rx_steering& operator=(const rx_steering&) = delete;
+    ~rx_steering() { sccsum_steer_destroy(_s); }
+    void close() {
+        sccsum_steer* s = _s;
+        _s = nullptr;
+        check(sccsum_steer_destroy(s), "sccsum_steer_destroy");
+    }
+
+    // bytes of 16-byte aligned device scratch a run over n packets needs
+    uint64_t workspace(uint64_t n) const noexcept { return sccsum_steer_workspace(_s, n); }
+
+    // mode SCCSUM_STEER_DISPATCH (forward_dst(src_cpu, hash)) or SCCSUM_STEER_HASH2CPU; a packet whose
+    // status lacks a `need` bit or has a `reject` bit is dropped (d_status null: none, masks 0).
+    // d_cpu[n] (0xFF = dropped) and d_order[n] may be null; d_first has ncpu + 2 entries.
+    void run(int mode, uint32_t src_cpu, const uint32_t* d_hash, const uint8_t* d_status, uint32_t need,
+             uint32_t reject, uint64_t n, uint8_t* d_cpu, uint32_t* d_order, uint32_t* d_first, void* d_workspace,
+             void* stream) const {
+        check(sccsum_steer_run(_s, mode, src_cpu, d_hash, d_status, need, reject, n, d_cpu, d_order, d_first,
+                               d_workspace, stream),
+              "sccsum_steer_run");
+    }
+
+    // qp::build_sw_reta (net.cc:214-231): cpus strictly ascending, as the reference's std::map iterates
+    static void build_reta(const uint32_t* cpus, const float* weights, uint32_t n, uint8_t (&reta)[128]) {
+        check(sccsum_steer_build_reta(cpus, weights, n, reta), "sccsum_steer_build_reta");
+    }
+
+    // one hash through the map on the host: device::hash2cpu (SCCSUM_STEER_HASH2CPU) / forward_dst
+    static uint32_t dest(const sccsum_steer_map& map, int mode, uint32_t src_cpu, uint32_t hash) {
+        const uint32_t d = sccsum_steer_dest(&map, mode, src_cpu, hash);
+        if (d == UINT32_MAX) check(SCCSUM_EINVAL, "sccsum_steer_dest");
+        return d;
+    }
 };
 
 }  // namespace net

@@ -456,6 +456,137 @@ def pseudo_seed(src_host: int, dst_host: int, proto: int, length: int) -> int:
     return int(native.load().sccsum_pseudo_seed(src_host, dst_host, proto, length & 0xFFFF))
 
 
+def build_reta(weights: dict) -> np.ndarray:
+    """sccsum_steer_build_reta: qp::build_sw_reta (net.cc:214-231) for a
+    {cpu: weight} map, iterated in ascending cpu order like the reference's
+    std::map; the 128-entry table as uint8."""
+    cpus = sorted(int(c) for c in weights)
+    if not cpus or cpus[0] < 0:
+        raise ValueError("build_reta: need at least one cpu >= 0")
+    c = np.array(cpus, dtype=np.uint32)
+    w = np.array([weights[k] for k in sorted(weights, key=int)], dtype=np.float32)
+    out = np.zeros(native.RETA_SIZE, dtype=np.uint8)
+    native.check(native.load().sccsum_steer_build_reta(c.ctypes.data, w.ctypes.data, len(cpus), out.ctypes.data),
+                 "sccsum_steer_build_reta")
+    return out
+
+
+def _steer_map(ncpu, sw_reta, hw_queues, redir, table_bits, sw_reta_set):
+    """(native.SteerMap, the numpy arrays it points into)."""
+    reta = np.ascontiguousarray(sw_reta, dtype=np.uint8)
+    if reta.ndim == 1:
+        reta = reta.reshape(1, -1)
+    if hw_queues is None:
+        hw_queues = reta.shape[0]
+    if reta.ndim != 2 or reta.shape != (int(hw_queues), native.RETA_SIZE):
+        raise ValueError(f"sw_reta: need [hw_queues={hw_queues}][{native.RETA_SIZE}] uint8 entries, got {reta.shape}")
+    rd = None if redir is None else np.ascontiguousarray(redir, dtype=np.uint8).ravel()
+    has = None if sw_reta_set is None else np.ascontiguousarray(sw_reta_set, dtype=np.uint8).ravel()
+    if has is not None and has.size != int(hw_queues):
+        raise ValueError(f"sw_reta_set: need {hw_queues} entries, got {has.size}")
+    m = native.SteerMap(int(ncpu), int(hw_queues), int(table_bits), 0 if rd is None else int(rd.size),
+                        None if rd is None else rd.ctypes.data, reta.ctypes.data,
+                        None if has is None else has.ctypes.data)
+    return m, (reta, rd, has)
+
+
+def steer_dest(hash_value: int, ncpu: int, sw_reta, hw_queues: int | None = None, redir=None, table_bits: int = 0,
+               sw_reta_set=None, mode: int = native.STEER_HASH2CPU, src_cpu: int = 0) -> int:
+    """sccsum_steer_dest: one hash through the map on the host (device::hash2cpu /
+    forward_dst, net.hh:291-305)."""
+    m, keep = _steer_map(ncpu, sw_reta, hw_queues, redir, table_bits, sw_reta_set)
+    d = int(native.load().sccsum_steer_dest(ctypes.addressof(m), int(mode), int(src_cpu), int(hash_value) & 0xFFFFFFFF))
+    del keep
+    if d == 0xFFFFFFFF:
+        raise ValueError("steer_dest: bad map or mode")
+    return d
+
+
+class Steer:
+    """sccsum_steer_*: rx steering of a batch on the device (include/sccsum.h,
+    "Rx steering"): every packet's destination shard from its RSS hash, and the
+    batch's packet indices grouped by shard in arrival order.
+
+        st = Steer(ncpu=16, sw_reta=build_reta({c: 1.0 for c in range(16)}))
+        cpu, order, first = st.run(hashes, status, need=ST_OK, reject=ST_MALFORMED | ST_RANGE)
+        # shard c's packets: order[first[c]:first[c + 1]]; the dropped ones: order[first[ncpu]:first[ncpu + 1]]
+
+    sw_reta is [hw_queues][128] (one row may be given flat); sw_reta_set marks
+    the queues that have one (None: all).  The object is immutable and may be
+    run from any thread on any stream of its device."""
+
+    def __init__(self, ncpu: int, sw_reta, hw_queues: int | None = None, redir=None, table_bits: int = 0,
+                 sw_reta_set=None, device: int = 0):
+        self._lib = native.load()
+        self._h = None
+        m, keep = _steer_map(ncpu, sw_reta, hw_queues, redir, table_bits, sw_reta_set)
+        h = ctypes.c_void_p()
+        native.check(self._lib.sccsum_steer_create(int(device), ctypes.addressof(m), ctypes.byref(h)),
+                     "sccsum_steer_create")
+        del keep
+        self._h = h
+        self.ncpu = int(ncpu)
+        self.device = torch.device("cuda", int(device))
+
+    @staticmethod
+    def check_args(dev, ncpu, hashes, status, need, reject, cpu, order, first) -> int:
+        """What run() refuses before any launch (the kernels trust the sizes); returns n."""
+        if (not isinstance(hashes, torch.Tensor) or hashes.dtype != torch.int32 or hashes.dim() != 1
+                or not hashes.is_contiguous() or hashes.device != dev):
+            raise ValueError(f"hashes: need a contiguous 1-D int32 tensor on {dev}")
+        n = int(hashes.numel())
+        _need(status, n, torch.uint8, "status", dev)
+        if status is None and (need or reject):
+            raise ValueError("need / reject masks without a status array")
+        _need(cpu, n, torch.uint8, "cpu", dev)
+        _need(order, n, torch.int32, "order", dev)
+        _need(first, ncpu + 2, torch.int32, "first", dev)
+        return n
+
+    def workspace_bytes(self, n: int) -> int:
+        return int(self._lib.sccsum_steer_workspace(self._h, int(n)))
+
+    def run(self, hashes: torch.Tensor, status: torch.Tensor | None = None, need: int = 0, reject: int = 0,
+            mode: int = native.STEER_HASH2CPU, src_cpu: int = 0, stream=None, cpu: torch.Tensor | None = None,
+            order: torch.Tensor | None = None, first: torch.Tensor | None = None,
+            workspace: torch.Tensor | None = None, want_cpu: bool = True, want_order: bool = True):
+        """(cpu uint8 [n], order int32 [n], first int32 [ncpu + 2]); cpu / order
+        are None when want_cpu / want_order is False and no tensor was passed.
+        Indices and counts are uint32 values in int32 tensors."""
+        if self._h is None:
+            raise ValueError("Steer is closed")
+        dev = self.device
+        n = self.check_args(dev, self.ncpu, hashes, status, need, reject, cpu, order, first)
+        if cpu is None and want_cpu:
+            cpu = _scratch(max(n, 1), dev, stream, torch.uint8)
+        if order is None and want_order:
+            order = _scratch(max(n, 1), dev, stream, torch.int32)
+        if first is None:
+            first = _scratch(self.ncpu + 2, dev, stream, torch.int32)
+        ws_bytes = self.workspace_bytes(n)
+        if workspace is None:
+            workspace = _scratch(ws_bytes, dev, stream)
+        _need(workspace, ws_bytes, torch.uint8, "workspace", dev)
+        if n == 0:  # an empty tensor has no address: nothing to drop, only first is written
+            status, need, reject = None, 0, 0
+        code = self._lib.sccsum_steer_run(self._h, int(mode), int(src_cpu), ctypes_ptr(hashes), _ptr(status),
+                                          int(need), int(reject), n, _ptr(cpu), _ptr(order), ctypes_ptr(first),
+                                          ctypes_ptr(workspace), _stream(stream))
+        native.check(code, "sccsum_steer_run")
+        return (None if cpu is None else cpu[:n]), (None if order is None else order[:n]), first[: self.ncpu + 2]
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            native.check(self._lib.sccsum_steer_destroy(h), "sccsum_steer_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

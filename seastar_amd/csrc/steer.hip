@@ -1,0 +1,532 @@
+// steer.hip — rx steering on the GPU: hash2cpu for a whole batch plus a STABLE
+// partition of the batch's packet indices by destination shard (sccsum.h,
+// "Rx steering").
+//
+// What it restates from the reference (paths relative to the reference tree):
+//   device::forward_dst   include/seastar/net/net.hh:291-300
+//   device::hash2cpu      net.hh:301-305
+//   device::hash2qid      net.hh:287-289, dpdk override src/net/dpdk.cc:505-508
+//   qp::build_sw_reta     src/net/net.cc:214-231
+//
+// Three dependent launches on the caller's stream (four past 31 shards), no
+// block ever waiting on another one:
+//   steer_count_kernel    one block per tile of kSteerTile packets: destination
+//                         of every packet (-> d_cpu), per-bucket counts of the
+//                         tile -> workspace[bucket][tile]
+//   steer_scan_kernel     ONE block: per bucket an exclusive scan over the
+//                         tiles (in place), then the bucket bases -> d_first;
+//                         with more than 32 buckets steer_scan_rows_kernel (one
+//                         block per bucket) and steer_scan_totals_kernel instead
+//   steer_scatter_kernel  one block per tile: destinations recomputed, each
+//                         packet's rank inside its tile computed from wave
+//                         match masks and a per-wave count table, index stored
+//                         at d_first[bucket] + workspace[bucket][tile] + rank
+// Bucket c < ncpu is shard c, bucket ncpu holds the dropped packets.  No
+// atomic decides a position: the only atomics are LDS adds into the count
+// kernel's histogram, whose sums do not depend on their order, so every
+// output byte is a function of the inputs alone.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <tuple>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "sccsum.h"
+#include "sccsum_diag.h"
+
+namespace steer {
+
+constexpr int kBlock = 256;              // threads per block of the count / scatter kernels
+constexpr int kWave = 64;
+constexpr int kWaves = kBlock / kWave;
+constexpr int kRounds = 8;               // packets per thread: round r of a tile is its packets [256 r, 256 r + 256)
+constexpr uint32_t kSteerTile = kBlock * kRounds;
+constexpr int kSlots = kRounds * kWaves; // (round, wave) pairs of a tile, in packet order
+constexpr int kMaxBuckets = 256;         // ncpu <= 255 shards + the drop bucket
+constexpr int kScanBlock = 1024;
+constexpr int kScanWaves = kScanBlock / kWave;
+constexpr uint32_t kScanOneBlockMax = 2 * kScanWaves;  // buckets the one-block scan takes (two rows per wave)
+constexpr uint32_t kRetaSize = 128;      // std::array<uint8_t, 128> (net.hh, qp::_sw_reta)
+constexpr uint32_t kMaxRedir = 512;
+constexpr uint32_t kMaxQueues = 256;
+constexpr int kMaxDevices = 64;
+
+// What the kernels need of a map (by value in the launch).  `reta` points at
+// the first row the launch uses: rows == 0 means every packet goes to `fixed`
+// (dispatch from a queue that has no _sw_reta), rows == 1 that one row decides
+// (dispatch), rows == hw_queues that hash2qid picks the row (hash2cpu).  A
+// queue without a _sw_reta has its row filled with its own index at create,
+// which is what forward_dst returns for it.
+struct Params {
+    const uint8_t* reta;   // device, rows x 128
+    const uint8_t* redir;  // device, redir_size entries (16-byte padded), or nullptr
+    uint32_t rows;
+    uint32_t hw_queues;
+    uint32_t redir_size;
+    uint32_t table_bits;
+    uint32_t ncpu;
+    uint32_t fixed;
+    uint32_t need;
+    uint32_t reject;
+};
+
+__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
+
+// Tables into LDS: lds[0 .. rows*128) the reta rows, then the redir table.
+__device__ __forceinline__ void load_tables(const Params& P, uint8_t* lds) {
+    const uint32_t reta_units = P.rows * (kRetaSize / 16);
+    const uint32_t redir_units = P.rows > 1 ? (P.redir_size + 15) / 16 : 0;
+    uint4* dst = reinterpret_cast<uint4*>(lds);
+    const uint4* src = reinterpret_cast<const uint4*>(P.reta);
+    for (uint32_t i = threadIdx.x; i < reta_units; i += kBlock) dst[i] = src[i];
+    const uint4* rsrc = reinterpret_cast<const uint4*>(P.redir);
+    for (uint32_t i = threadIdx.x; i < redir_units; i += kBlock) dst[reta_units + i] = rsrc[i];
+}
+
+// Bucket of one packet: ncpu for a dropped one.
+__device__ __forceinline__ uint32_t bucket_of(const Params& P, const uint8_t* lds, uint32_t hash, uint32_t st,
+                                              bool has_status) {
+    if (has_status && ((st & P.need) != P.need || (st & P.reject) != 0)) return P.ncpu;
+    if (P.rows == 0) return P.fixed;
+    uint32_t q = 0;
+    if (P.rows > 1) {
+        q = P.redir_size ? lds[P.rows * kRetaSize + (hash & (P.redir_size - 1))] : hash % P.hw_queues;
+    }
+    return lds[q * kRetaSize + ((hash >> P.table_bits) & (kRetaSize - 1))];
+}
+
+// The lanes of the wave whose bucket equals this lane's, among the valid ones:
+// eight ballots, one per bit of the 8-bit bucket.
+__device__ __forceinline__ uint64_t match_bucket(uint32_t b, bool valid) {
+    uint64_t m = __ballot(valid);
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+        const uint64_t set = __ballot((b >> bit) & 1u);
+        m &= ((b >> bit) & 1u) ? set : ~set;
+    }
+    return m;
+}
+
+__device__ __forceinline__ uint64_t lanes_below() { return (uint64_t(1) << lane_id()) - 1u; }
+
+// Loads a tile's hashes and status bytes (all loads issued before any use) and
+// turns them into buckets.
+__device__ __forceinline__ void tile_buckets(const Params& P, const uint8_t* lds, const uint32_t* __restrict__ d_hash,
+                                             const uint8_t* __restrict__ d_status, uint64_t n, uint64_t first,
+                                             uint32_t (&b)[kRounds]) {
+    uint32_t h[kRounds];
+    uint32_t st[kRounds];
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint64_t i = first + uint64_t(r) * kBlock + threadIdx.x;
+        h[r] = i < n ? d_hash[i] : 0u;
+        st[r] = (d_status && i < n) ? d_status[i] : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) b[r] = bucket_of(P, lds, h[r], st[r], d_status != nullptr);
+}
+
+extern __shared__ uint4 steer_dyn_lds[];
+
+__global__ __launch_bounds__(kBlock) void steer_count_kernel(const uint32_t* __restrict__ d_hash,
+                                                             const uint8_t* __restrict__ d_status, uint64_t n,
+                                                             uint8_t* __restrict__ d_cpu, uint32_t* __restrict__ ws,
+                                                             uint32_t tile_pitch, Params P) {
+    __shared__ uint32_t hist[kMaxBuckets];
+    uint8_t* const lds = reinterpret_cast<uint8_t*>(steer_dyn_lds);
+    const uint32_t buckets = P.ncpu + 1;
+    load_tables(P, lds);
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t first = uint64_t(blockIdx.x) * kSteerTile;
+    uint32_t b[kRounds];
+    tile_buckets(P, lds, d_hash, d_status, n, first, b);
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint64_t i = first + uint64_t(r) * kBlock + threadIdx.x;
+        const bool valid = i < n;
+        const uint64_t m = match_bucket(b[r], valid);
+        // one LDS add per distinct bucket of the wave: only a count comes out
+        if (valid && (m & lanes_below()) == 0) atomicAdd(&hist[b[r]], static_cast<uint32_t>(__popcll(m)));
+        if (valid && d_cpu) d_cpu[i] = b[r] == P.ncpu ? uint8_t(0xFF) : static_cast<uint8_t>(b[r]);
+    }
+    __syncthreads();
+    if (threadIdx.x < buckets) ws[uint64_t(threadIdx.x) * tile_pitch + blockIdx.x] = hist[threadIdx.x];
+}
+
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, kWave);
+        if (lane_id() >= static_cast<uint32_t>(d)) v += o;
+    }
+    return v;
+}
+
+// One wave scans one bucket's row of per-tile counts in place (exclusive): each
+// lane takes four consecutive tiles (one 16-byte load), the lanes' sums are
+// scanned across the wave, 256 tiles at a time with the sum carried along.
+// Returns the row's total (the same in every lane).
+__device__ __forceinline__ uint32_t scan_row(uint32_t* __restrict__ ws, uint32_t b, uint32_t ntiles,
+                                             uint32_t tile_pitch) {
+    uint4* const row = reinterpret_cast<uint4*>(ws + uint64_t(b) * tile_pitch);
+    const uint32_t lane = lane_id();
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < ntiles; base += kWave * 4) {
+        const uint32_t t = base + lane * 4;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (t < ntiles) v = row[t / 4];
+        if (t + 1 >= ntiles) v.y = 0;  // the row's padding up to tile_pitch
+        if (t + 2 >= ntiles) v.z = 0;
+        if (t + 3 >= ntiles) v.w = 0;
+        const uint32_t sum = v.x + v.y + v.z + v.w;
+        const uint32_t incl = wave_inclusive_scan(sum);
+        const uint32_t ex = carry + incl - sum;
+        if (t < ntiles) row[t / 4] = make_uint4(ex, ex + v.x, ex + v.x + v.y, ex + v.x + v.y + v.z);
+        carry += __shfl(incl, kWave - 1, kWave);
+    }
+    return carry;
+}
+
+// One wave: the bucket totals scanned into d_first (ncpu + 2 entries).
+__device__ __forceinline__ void scan_totals(const uint32_t* total, uint32_t buckets, uint32_t* __restrict__ d_first) {
+    const uint32_t lane = lane_id();
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < buckets; base += kWave) {
+        const uint32_t b = base + lane;
+        const uint32_t c = b < buckets ? total[b] : 0u;
+        const uint32_t incl = wave_inclusive_scan(c);
+        if (b < buckets) d_first[b] = carry + incl - c;
+        carry += __shfl(incl, kWave - 1, kWave);
+    }
+    if (lane == 0) d_first[buckets] = carry;
+}
+
+// Few buckets (at most kScanOneBlockMax): ONE block does both, wave w taking
+// the rows of buckets w, w + 16, ...
+__global__ __launch_bounds__(kScanBlock) void steer_scan_kernel(uint32_t* __restrict__ ws, uint32_t ntiles,
+                                                                uint32_t tile_pitch, uint32_t buckets,
+                                                                uint32_t* __restrict__ d_first) {
+    __shared__ uint32_t total[kMaxBuckets];
+    const uint32_t wave = threadIdx.x / kWave;
+    for (uint32_t b = wave; b < buckets; b += kScanWaves) {
+        const uint32_t sum = scan_row(ws, b, ntiles, tile_pitch);
+        if (lane_id() == 0) total[b] = sum;
+    }
+    __syncthreads();
+    if (wave == 0) scan_totals(total, buckets, d_first);
+}
+
+// Many buckets: one block (one wave) per bucket scans its row and leaves the
+// total behind the rows; a second launch of one wave scans the totals.  One
+// compute unit alone takes 24 us for the 257 rows of 512 tiles of a
+// 1 Mi-packet batch at 255 shards, whether or not its loads are batched
+// (DESIGN.md §5.12): the rows are spread over the device instead.
+__global__ __launch_bounds__(kWave) void steer_scan_rows_kernel(uint32_t* __restrict__ ws, uint32_t ntiles,
+                                                                uint32_t tile_pitch, uint32_t* __restrict__ totals) {
+    const uint32_t sum = scan_row(ws, blockIdx.x, ntiles, tile_pitch);
+    if (lane_id() == 0) totals[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(kWave) void steer_scan_totals_kernel(const uint32_t* __restrict__ totals, uint32_t buckets,
+                                                                  uint32_t* __restrict__ d_first) {
+    scan_totals(totals, buckets, d_first);
+}
+
+__global__ __launch_bounds__(kBlock) void steer_scatter_kernel(const uint32_t* __restrict__ d_hash,
+                                                               const uint8_t* __restrict__ d_status, uint64_t n,
+                                                               const uint32_t* __restrict__ ws, uint32_t tile_pitch,
+                                                               const uint32_t* __restrict__ d_first,
+                                                               uint32_t* __restrict__ d_order, Params P) {
+    // cnt[slot][bucket]: packets of the bucket in (round, wave) pair `slot`, then
+    // their offset inside the tile (at most 2048: 16 bits); base[bucket]: where
+    // the tile's packets of the bucket start in d_order
+    __shared__ uint16_t cnt[kSlots][kMaxBuckets];
+    __shared__ uint32_t base[kMaxBuckets];
+    uint8_t* const lds = reinterpret_cast<uint8_t*>(steer_dyn_lds);
+    const uint32_t buckets = P.ncpu + 1;
+    const uint32_t wave = threadIdx.x / kWave;
+    load_tables(P, lds);
+    if (threadIdx.x < buckets) {
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) cnt[s][threadIdx.x] = 0;
+        base[threadIdx.x] = d_first[threadIdx.x] + ws[uint64_t(threadIdx.x) * tile_pitch + blockIdx.x];
+    }
+    __syncthreads();
+    const uint64_t first = uint64_t(blockIdx.x) * kSteerTile;
+    uint32_t b[kRounds];
+    uint32_t rank[kRounds];
+    tile_buckets(P, lds, d_hash, d_status, n, first, b);
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const bool valid = first + uint64_t(r) * kBlock + threadIdx.x < n;
+        const uint64_t m = match_bucket(b[r], valid);
+        rank[r] = static_cast<uint32_t>(__popcll(m & lanes_below()));
+        if (valid && rank[r] == 0) cnt[r * kWaves + wave][b[r]] = static_cast<uint16_t>(__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < buckets) {
+        uint32_t run = 0;
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const uint32_t c = cnt[s][threadIdx.x];
+            cnt[s][threadIdx.x] = static_cast<uint16_t>(run);
+            run += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint64_t i = first + uint64_t(r) * kBlock + threadIdx.x;
+        if (i < n) {
+            const uint64_t pos = uint64_t(base[b[r]]) + cnt[r * kWaves + wave][b[r]] + rank[r];
+            if (pos < n) d_order[pos] = static_cast<uint32_t>(i);  // always true for consistent inputs
+        }
+    }
+}
+
+// ---------------------------------------------------------------- host side
+
+template <typename... P, typename... A>
+hipError_t launch_kernel(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... a) {
+    static_assert(sizeof...(P) == sizeof...(A), "argument count");
+    std::tuple<std::decay_t<P>...> t(static_cast<std::decay_t<P>>(std::forward<A>(a))...);
+    void* args[sizeof...(P)];
+    std::apply([&](auto&... x) {
+        size_t i = 0;
+        ((args[i++] = static_cast<void*>(&x)), ...);
+    }, t);
+    return hipLaunchKernel(reinterpret_cast<const void*>(k), grid, block, args, lds, s);
+}
+
+bool power_of_two(uint32_t v) { return v != 0 && (v & (v - 1)) == 0; }
+
+// The scalar fields of a map (no table is read).
+bool map_shape_ok(const sccsum_steer_map* m) {
+    return m && m->ncpu >= 1 && m->ncpu <= 255 && m->hw_queues >= 1 && m->hw_queues <= kMaxQueues &&
+           m->table_bits <= 31 && (m->redir_size == 0 || (power_of_two(m->redir_size) && m->redir_size <= kMaxRedir)) &&
+           (m->redir != nullptr) == (m->redir_size != 0) && m->sw_reta != nullptr;
+}
+
+bool queue_has_reta(const sccsum_steer_map* m, uint32_t q) { return !m->sw_reta_set || m->sw_reta_set[q] != 0; }
+
+// forward_dst(src, hash), net.hh:291-300; a src past the hardware queues is a
+// proxy queue, which never has a _sw_reta (net.cc:173-212).
+uint32_t forward_dst(const sccsum_steer_map* m, uint32_t src, uint32_t hash) {
+    if (src >= m->hw_queues || !queue_has_reta(m, src)) return src;
+    return m->sw_reta[src * kRetaSize + ((hash >> m->table_bits) % kRetaSize)];
+}
+
+uint32_t hash2qid(const sccsum_steer_map* m, uint32_t hash) {
+    return m->redir_size ? m->redir[hash & (m->redir_size - 1)] : hash % m->hw_queues;
+}
+
+}  // namespace steer
+
+struct sccsum_steer {
+    int device = 0;
+    sccsum_steer_map map{};           // scalar fields; the table pointers are the host copies below
+    std::vector<uint8_t> reta;        // [hw_queues][128], rows of queues without a _sw_reta filled with the queue
+    std::vector<uint8_t> has_reta;    // [hw_queues]
+    uint8_t* d_tables = nullptr;      // device: reta rows, then the redir table (16-byte padded)
+    uint32_t redir_off = 0;
+};
+
+extern "C" {
+
+int sccsum_steer_tile_packets(void) { return static_cast<int>(steer::kSteerTile); }
+
+int sccsum_steer_build_reta(const uint32_t* cpus, const float* weights, uint32_t n, uint8_t reta[128]) {
+    if (!cpus || !weights || !reta || n == 0 || n > 255) return SCCSUM_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        // the std::map iterates in ascending cpu order; 0xFF is the drop mark
+        if (cpus[i] > 254 || (i && cpus[i] <= cpus[i - 1]) || !(weights[i] >= 0.0f) || std::isinf(weights[i])) {
+            return SCCSUM_EINVAL;
+        }
+    }
+    // net.cc:214-231, the same float arithmetic: accum / total * 128 in float, - 0.5 in double
+    float total_weight = 0;
+    for (uint32_t i = 0; i < n; ++i) total_weight += weights[i];
+    float accum = 0;
+    unsigned idx = 0;
+    uint8_t out[steer::kRetaSize];
+    for (uint32_t i = 0; i < n; ++i) {
+        accum += weights[i];
+        while (idx < steer::kRetaSize && idx < (accum / total_weight * steer::kRetaSize - 0.5)) {
+            out[idx++] = static_cast<uint8_t>(cpus[i]);
+        }
+    }
+    if (idx != steer::kRetaSize) return SCCSUM_EINVAL;  // a zero total: the reference would leave entries unset
+    std::memcpy(reta, out, sizeof(out));
+    return SCCSUM_OK;
+}
+
+uint32_t sccsum_steer_dest(const sccsum_steer_map* map, int mode, uint32_t src_cpu, uint32_t hash) {
+    if (!steer::map_shape_ok(map)) return UINT32_MAX;
+    if (mode == SCCSUM_STEER_DISPATCH) return steer::forward_dst(map, src_cpu, hash);
+    if (mode == SCCSUM_STEER_HASH2CPU) return steer::forward_dst(map, steer::hash2qid(map, hash), hash);
+    return UINT32_MAX;
+}
+
+int sccsum_steer_create(int device, const sccsum_steer_map* map, sccsum_steer** out) {
+    using namespace steer;
+    if (!out) return SCCSUM_EINVAL;
+    *out = nullptr;
+    if (!map_shape_ok(map)) return SCCSUM_EINVAL;
+    for (uint32_t i = 0; i < map->redir_size; ++i) {
+        if (map->redir[i] >= map->hw_queues) return SCCSUM_EINVAL;
+    }
+    for (uint32_t q = 0; q < map->hw_queues; ++q) {
+        if (!queue_has_reta(map, q)) {
+            if (q >= map->ncpu) return SCCSUM_EINVAL;  // forward_dst would return the queue itself
+            continue;
+        }
+        for (uint32_t i = 0; i < kRetaSize; ++i) {
+            if (map->sw_reta[q * kRetaSize + i] >= map->ncpu) return SCCSUM_EINVAL;
+        }
+    }
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess) return e == hipErrorNoDevice ? SCCSUM_ENODEV : static_cast<int>(e);
+    if (device < 0 || device >= ndev || device >= kMaxDevices) return SCCSUM_ENODEV;
+    auto* s = new (std::nothrow) sccsum_steer;
+    if (!s) return static_cast<int>(hipErrorOutOfMemory);
+    s->device = device;
+    s->map = *map;
+    s->reta.resize(size_t(map->hw_queues) * kRetaSize);
+    s->has_reta.resize(map->hw_queues);
+    for (uint32_t q = 0; q < map->hw_queues; ++q) {
+        s->has_reta[q] = queue_has_reta(map, q);
+        if (s->has_reta[q]) {
+            std::memcpy(&s->reta[size_t(q) * kRetaSize], map->sw_reta + size_t(q) * kRetaSize, kRetaSize);
+        } else {
+            std::memset(&s->reta[size_t(q) * kRetaSize], static_cast<int>(q), kRetaSize);
+        }
+    }
+    s->redir_off = static_cast<uint32_t>(s->reta.size());
+    std::vector<uint8_t> blob(s->redir_off + ((map->redir_size + 15u) & ~15u), 0);
+    std::memcpy(blob.data(), s->reta.data(), s->reta.size());
+    if (map->redir_size) std::memcpy(blob.data() + s->redir_off, map->redir, map->redir_size);
+    s->map.redir = nullptr;
+    s->map.sw_reta = nullptr;
+    s->map.sw_reta_set = nullptr;
+    int cur = 0;
+    e = hipGetDevice(&cur);
+    if (e == hipSuccess) e = hipSetDevice(device);
+    if (e == hipSuccess) {
+        void* d = nullptr;
+        e = hipMalloc(&d, blob.size());
+        if (e == hipSuccess) {
+            s->d_tables = static_cast<uint8_t*>(d);
+            e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
+        }
+        (void)hipSetDevice(cur);  // the caller's binding is put back
+    }
+    if (e != hipSuccess) {
+        if (s->d_tables) (void)hipFree(s->d_tables);
+        delete s;
+        return static_cast<int>(e);
+    }
+    *out = s;
+    return SCCSUM_OK;
+}
+
+int sccsum_steer_destroy(sccsum_steer* s) {
+    if (!s) return SCCSUM_OK;
+    const hipError_t e = s->d_tables ? hipFree(s->d_tables) : hipSuccess;
+    delete s;
+    return static_cast<int>(e);
+}
+
+uint64_t sccsum_steer_workspace(const sccsum_steer* s, uint64_t n) {
+    if (!s) return 0;
+    const uint64_t ntiles = (n + steer::kSteerTile - 1) / steer::kSteerTile;
+    const uint64_t pitch = (ntiles + 3) & ~uint64_t(3);
+    // the per-tile counts [ncpu + 1][pitch], then the bucket totals of the many-bucket scan
+    return uint64_t(s->map.ncpu + 1) * pitch * 4u + steer::kMaxBuckets * 4u;
+}
+
+int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const uint32_t* d_hash,
+                     const uint8_t* d_status, uint32_t need, uint32_t reject, uint64_t n, uint8_t* d_cpu,
+                     uint32_t* d_order, uint32_t* d_first, void* d_workspace, void* stream) {
+    using namespace steer;
+    if (!s || (mode != SCCSUM_STEER_DISPATCH && mode != SCCSUM_STEER_HASH2CPU)) return SCCSUM_EINVAL;
+    if (!d_status && (need != 0 || reject != 0)) return SCCSUM_EINVAL;
+    if (n > 0xFFFFFFFFull) return SCCSUM_EINVAL;  // packet indices are 32-bit
+    if (reinterpret_cast<uintptr_t>(d_first) & 3u) return SCCSUM_EINVAL;
+    Params P{};
+    P.hw_queues = s->map.hw_queues;
+    P.redir_size = s->map.redir_size;
+    P.table_bits = s->map.table_bits;
+    P.ncpu = s->map.ncpu;
+    P.need = need;
+    P.reject = reject;
+    P.redir = s->map.redir_size ? s->d_tables + s->redir_off : nullptr;
+    if (mode == SCCSUM_STEER_DISPATCH) {
+        if (src_cpu < s->map.hw_queues && s->has_reta[src_cpu]) {
+            P.rows = 1;
+            P.reta = s->d_tables + size_t(src_cpu) * kRetaSize;
+        } else {
+            if (src_cpu >= s->map.ncpu) return SCCSUM_EINVAL;  // forward_dst returns src_cpu itself
+            P.rows = 0;
+            P.fixed = src_cpu;
+            P.reta = s->d_tables;
+        }
+    } else {
+        P.rows = s->map.hw_queues;
+        P.reta = s->d_tables;
+    }
+    if (n == 0 && !d_first) return SCCSUM_OK;
+    if (!d_first) return SCCSUM_EINVAL;
+    if (n > 0 && (!d_hash || (reinterpret_cast<uintptr_t>(d_hash) & 3u) || (reinterpret_cast<uintptr_t>(d_order) & 3u) ||
+                  !d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 15u))) {
+        return SCCSUM_EINVAL;
+    }
+    // the launches run on the stream's device, where the tables must lie
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return static_cast<int>(e);
+    if (st != nullptr) {
+        hipDevice_t sd = -1;
+        e = hipStreamGetDevice(st, &sd);
+        if (e != hipSuccess) return static_cast<int>(e);
+        dev = sd;
+    }
+    if (dev != s->device) return SCCSUM_EINVAL;
+
+    const uint32_t ntiles = static_cast<uint32_t>((n + kSteerTile - 1) / kSteerTile);
+    const uint32_t pitch = (ntiles + 3u) & ~3u;
+    const uint32_t buckets = P.ncpu + 1;
+    uint32_t* const ws = static_cast<uint32_t*>(d_workspace);
+    const size_t lds = size_t(P.rows) * kRetaSize + (P.rows > 1 ? ((P.redir_size + 15u) & ~15u) : 0u);
+    if (ntiles) {
+        e = launch_kernel(steer_count_kernel, dim3(ntiles), dim3(kBlock), lds, st, d_hash, d_status, n, d_cpu, ws, pitch,
+                          P);
+        if (e != hipSuccess) return static_cast<int>(e);
+    }
+    if (buckets <= kScanOneBlockMax || ntiles == 0) {
+        e = launch_kernel(steer_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, ws, ntiles, pitch, buckets, d_first);
+    } else {
+        uint32_t* const totals = ws + uint64_t(buckets) * pitch;
+        e = launch_kernel(steer_scan_rows_kernel, dim3(buckets), dim3(kWave), 0, st, ws, ntiles, pitch, totals);
+        if (e == hipSuccess) {
+            e = launch_kernel(steer_scan_totals_kernel, dim3(1), dim3(kWave), 0, st, static_cast<const uint32_t*>(totals),
+                              buckets, d_first);
+        }
+    }
+    if (e != hipSuccess) return static_cast<int>(e);
+    if (ntiles && d_order) {
+        e = launch_kernel(steer_scatter_kernel, dim3(ntiles), dim3(kBlock), lds, st, d_hash, d_status, n,
+                          static_cast<const uint32_t*>(ws), pitch, static_cast<const uint32_t*>(d_first), d_order, P);
+        if (e != hipSuccess) return static_cast<int>(e);
+    }
+    return SCCSUM_OK;
+}
+
+}  // extern "C"

@@ -114,6 +114,14 @@ _PROTOS = {
     "sccsum_engine_wait": (ctypes.c_int, [_vp, _u64, _u64]),
     "sccsum_engine_stop": (ctypes.c_int, [_vp]),
     "sccsum_engine_destroy": (ctypes.c_int, [_vp]),
+    "sccsum_steer_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "sccsum_steer_destroy": (ctypes.c_int, [_vp]),
+    "sccsum_steer_workspace": (_u64, [_vp, _u64]),
+    "sccsum_steer_run": (ctypes.c_int, [_vp, ctypes.c_int, _u32, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "sccsum_steer_dest": (_u32, [_vp, ctypes.c_int, _u32, _u32]),
+    "sccsum_steer_build_reta": (ctypes.c_int, [_vp, _vp, _u32, _vp]),
+    "sccsum_steer_tile_packets": (ctypes.c_int, []),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -142,6 +150,19 @@ class EngineOpts(ctypes.Structure):
     """sccsum_engine_opts: a resident engine's limits (0 = the default)."""
     _fields_ = [("ring_slots", ctypes.c_uint32), ("max_in_flight", ctypes.c_uint32), ("idle_ms", ctypes.c_uint32),
                 ("dep_ms", ctypes.c_uint32), ("producer_in_flight", ctypes.c_uint32)]
+
+
+STEER_DISPATCH = 0
+STEER_HASH2CPU = 1
+STEER_DROPPED = 0xFF  # d_cpu of a dropped packet
+RETA_SIZE = 128
+
+
+class SteerMap(ctypes.Structure):
+    """sccsum_steer_map: the tables rx steering sends a hash through (host memory)."""
+    _fields_ = [("ncpu", ctypes.c_uint32), ("hw_queues", ctypes.c_uint32), ("table_bits", ctypes.c_uint32),
+                ("redir_size", ctypes.c_uint32), ("redir", ctypes.c_void_p), ("sw_reta", ctypes.c_void_p),
+                ("sw_reta_set", ctypes.c_void_p)]
 
 
 class Fragment(ctypes.Structure):
