@@ -37,6 +37,10 @@
  *                       drops of src/net/ip.cc:121-144, plus the per-shard packet lists
  *                       their forward() calls fill; sccsum_steer_build_reta =
  *                       qp::build_sw_reta src/net/net.cc:214-231
+ *   sccsum_ipv4_send    N x ipv4::send  src/net/ip.cc:244-299: the IPv4 header it prepends
+ *                       (249-281) and, past the MTU (needs_frag, ip.cc:100-111), the cut
+ *                       into fragments (283-294), as header + payload fragment lists —
+ *                       no payload byte moves; sccsum_ipv4_send_plan = the count for one
  *   sccsum_pseudo_seed  ipv4_traits::{tcp,udp}_pseudo_header_checksum
  *                       include/seastar/net/ip.hh:70-75 (host arithmetic, O(1))
  *
@@ -113,7 +117,8 @@ extern "C" {
  * descriptor array when no packet has fragments; sccsum_engine_stop / _destroy
  * report SCCSUM_EIDLE only when a published step was left undone.
  * 4, additive (round 7): sccsum_ipv4_fill_desc, sccsum_burst_set_fill.
- * 4, additive (round 8): sccsum_steer_* (rx steering). */
+ * 4, additive (round 8): sccsum_steer_* (rx steering).
+ * 4, additive (round 9): sccsum_ipv4_send* (tx send). */
 #define SCCSUM_ABI_VERSION 4
 
 #define SCCSUM_OK 0
@@ -725,6 +730,115 @@ int sccsum_ipv4_frames_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_
 int sccsum_ipv4_fill_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                           const uint32_t* d_len, void* d_stage, uint16_t* d_out2, uint8_t* d_status,
                           uint64_t n, uint32_t max_len, uint32_t mode, void* stream);
+
+/* ---- Tx send: ipv4::send for a batch of L4 datagrams ---------------------------
+ * What ipv4::send (ip.cc:244-299) does to one L4 datagram, for a whole batch on
+ * the device: the 20-byte IPv4 header it prepends and, for a datagram that does
+ * not fit the MTU (needs_frag, ip.cc:100-111), the cut into pieces.  Like the
+ * reference, which shares the payload (p.share(offset, can_send)) and prepends
+ * a header, NO payload byte moves: per wire frame the call writes one header and
+ * two sccsum_gather_desc records, so its outputs are the arguments of
+ * sccsum_ipv4_frames_desc, sccsum_ipv4_fill_desc and sccsum_spans_desc as they
+ * stand, and sccsum_gather(d_desc, 2 * frames, dst) materialises the packed
+ * wire frames.
+ *
+ * Input.  Datagram i of n is d_l4[d_off[i] .. + d_len[i]): L4 header + payload,
+ * as ipv4::send receives `p`; d_dst[i] its destination (host order), d_proto[i]
+ * its protocol, d_id[i] its identification (d_id NULL: 0, what the reference
+ * writes, ip.cc:255).  opts: the source address (host order), the MTU
+ * (68..65535) and SCCSUM_SEND_* flags.
+ *
+ * The cut.  needs_frag = len + 20 > mtu && !((proto == 6 && TSO) || (proto ==
+ * 17 && UFO)).  A datagram that needs none is ONE frame with frag = 0 (an empty
+ * datagram: a header-only frame).  Otherwise it is cut, in order, into pieces
+ * of can_send = min(mtu - 20, remaining) bytes with
+ * frag = (remaining_after > 0) << 13 | (offset / 8).  The division TRUNCATES,
+ * exactly as the reference's does: with mtu - 20 not a multiple of 8 the
+ * offsets are the reference's, not RFC 791's.
+ *
+ * The header of a frame: 0x45, 0, len = 20 + piece, id, frag, ttl 64, proto,
+ * csum, src, dst (16- and 32-bit fields big-endian); csum = the RFC 1071
+ * checksum of the 20 bytes with the field zero, computed from the fields, or 0
+ * with SCCSUM_SEND_NO_IP_CSUM (tx_csum_ip_offload, ip.cc:271-273).
+ *
+ * Outputs, frame f (frames in datagram order, then piece order) of datagram i,
+ * its piece at datagram offset o:
+ *   d_hdr[20 f .. 20 f + 20)   the header
+ *   d_out_off[f]               the frame's position in a PACKED layout: frames
+ *                              back to back from 0
+ *   d_out_len[f]               20 + piece
+ *   d_desc[2f]                 {d_hdr + 20 f, d_out_off[f], 20}
+ *   d_desc[2f + 1]             {d_l4 + d_off[i] + o, d_out_off[f] + 20, piece}
+ *   d_first[f] = 2f            plus one closing entry after the last frame
+ *   d_dgram_first[i]           datagram i's first frame; n + 1 entries
+ *   d_status[i]  (required)    SCCSUM_ST_OK: emitted.  SCCSUM_ST_RANGE:
+ *                              [off, off + len) is not inside [0, l4_bytes_len)
+ *                              (the 64-bit test of sccsum_spans).
+ *                              SCCSUM_ST_MALFORMED: len > 65515 (the reference's
+ *                              uint16_t arithmetic would wrap).  Both bits when
+ *                              both hold.  A refused datagram has no frame:
+ *                              d_dgram_first[i + 1] == d_dgram_first[i].
+ *   d_total[3]                 {frames all valid datagrams need, layout bytes
+ *                              they need, datagrams emitted (the prefix)}
+ *
+ * Capacity, a prefix rule.  Datagram i is emitted only if over datagrams 0..i
+ * the frames are <= max_frames (itself <= 2^31 - 1) and the layout bytes
+ * <= max_out_bytes (itself <= 2^32 - 1: dst_off is 32-bit).  From the first
+ * datagram that does not fit onward nothing is emitted: those datagrams' status
+ * is 0 and their d_dgram_first entries (the closing one included) repeat the
+ * number of frames emitted.  No per-frame array is written past what was
+ * emitted (d_first: past its closing entry), so d_hdr holds 20 * max_frames
+ * bytes, d_desc 2 * max_frames records, d_first max_frames + 1 entries,
+ * d_out_off / d_out_len max_frames.  d_total reports the full need: a rerun
+ * with those caps emits everything.
+ *
+ * SCCSUM_SEND_L4: d_l4sum[i] — what sccsum_spans returned for the datagram with
+ * its pseudo-header seed and a zero field — is stored at UDP +6 (len >= 8) or
+ * TCP +16 (len >= 20) of every emitted datagram before the cut; other
+ * protocols and shorter datagrams are left alone.  It is the call's only write
+ * into d_l4; d_l4sum must be NULL without the flag.
+ *
+ * Four small kernels on `stream` (count, scan, place, emit), one chain of plain
+ * dependent launches: no allocation, no memset, no host synchronisation, no
+ * atomic deciding a position — two runs give identical bytes; capturable.
+ * d_workspace: sccsum_ipv4_send_workspace(n) bytes of device scratch, 16-byte
+ * aligned.  Alignment: d_off, d_out_off, d_total and d_desc 8 bytes; d_len,
+ * d_dst, d_first, d_out_len and d_dgram_first 4; d_id, d_l4sum 2; d_l4 and
+ * d_hdr any (a 4-byte aligned d_hdr is stored as words).  SCCSUM_EINVAL before any device
+ * work: mtu outside 68..65535, unknown flags, a NULL required pointer,
+ * misalignment, a cap out of range, n > 2^32 - 1, d_l4sum without / the flag
+ * without d_l4sum, a stream of another device.  n == 0 writes d_total,
+ * d_dgram_first[0] (and d_first[0] when d_first is given) and is SCCSUM_OK;
+ * the other arrays may then be NULL. */
+#define SCCSUM_SEND_TSO        0x01u /* hw_features().tx_tso: a TCP datagram is never cut (ip.cc:105) */
+#define SCCSUM_SEND_UFO        0x02u /* hw_features().tx_ufo: a UDP datagram is never cut (ip.cc:106) */
+#define SCCSUM_SEND_NO_IP_CSUM 0x04u /* tx_csum_ip_offload: csum field left 0 (ip.cc:271-273) */
+#define SCCSUM_SEND_L4         0x08u /* store d_l4sum[i] into datagram i's L4 field before the cut */
+
+typedef struct sccsum_send_opts {
+    uint32_t src_host; /* ipv4::_host_address, host order */
+    uint32_t mtu;      /* hw_features().mtu, 68..65535 */
+    uint32_t flags;
+} sccsum_send_opts;
+
+/* O(1) host arithmetic for one datagram (like sccsum_steer_dest): frames and
+ * layout bytes ipv4::send makes of an L4 datagram of l4_len bytes; 0 frames
+ * for l4_len > 65515 (SCCSUM_OK: the datagram would be refused) or bad opts
+ * (SCCSUM_EINVAL, as for a NULL pointer). */
+int sccsum_ipv4_send_plan(const sccsum_send_opts* opts, uint32_t l4_len, uint8_t proto,
+                          uint32_t* nframes, uint64_t* out_bytes);
+
+uint64_t sccsum_ipv4_send_workspace(uint64_t n);
+
+int sccsum_ipv4_send(const sccsum_send_opts* opts,
+                     void* d_l4, uint64_t l4_bytes_len, const uint64_t* d_off, const uint32_t* d_len,
+                     const uint32_t* d_dst, const uint8_t* d_proto, const uint16_t* d_id,
+                     const uint16_t* d_l4sum, uint64_t n,
+                     uint64_t max_frames, uint64_t max_out_bytes,
+                     uint8_t* d_hdr, sccsum_gather_desc* d_desc, uint32_t* d_first,
+                     uint64_t* d_out_off, uint32_t* d_out_len,
+                     uint32_t* d_dgram_first, uint8_t* d_status, uint64_t* d_total,
+                     void* d_workspace, void* stream);
 
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);

@@ -112,6 +112,12 @@ int sccsum_set_burst_fused(int on);
  * tests are built around it). */
 int sccsum_steer_tile_packets(void);
 
+/* Tx send (sccsum_ipv4_send): the datagrams of one tile of its count and place
+ * kernels, and the frames of one tile of its emit kernel (constants of the
+ * build; the edge-size tests are built around them). */
+int sccsum_send_tile_datagrams(void);
+int sccsum_send_emit_tile_frames(void);
+
 #ifdef __cplusplus
 }
 #endif

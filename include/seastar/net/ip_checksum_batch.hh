@@ -20,6 +20,8 @@
 //   toeplitz_hash(rss_key(), forward_hash)  net.cc:330-341    ipv4_rss(batch, key, ...) / ipv4_frames_rss(...)
 //   hash2cpu / forward_dst + forward()  net.hh:287-305,       rx_steering (shard of every packet + the batch's
 //       net.cc:330-344, ip.cc:197                                 indices grouped by shard, in arrival order)
+//   ipv4::send: the header it prepends and the cut past the    tx_sender (headers + header / payload fragment
+//       MTU  ip.cc:100-111, 244-299                               lists for a batch of L4 datagrams; no copy)
 //   per packet as qp::poll_tx / DPDK rx hand them over        burst_queue (host packets, async completion)
 //       net.cc:81-105, dpdk.cc:2190-2204
 //   a shard's steady stream of bursts, polled like its queues  resident_engine (one grid, steps streamed in;
@@ -380,6 +382,76 @@ public:
         const uint32_t d = sccsum_steer_dest(&map, mode, src_cpu, hash);
         if (d == UINT32_MAX) check(SCCSUM_EINVAL, "sccsum_steer_dest");
         return d;
+    }
+};
+
+// Tx send (<sccsum.h> sccsum_ipv4_send*): ipv4::send (ip.cc:244-299) for a
+// batch of L4 datagrams that lie in device memory — every frame's IPv4 header
+// and, for a datagram past the MTU (needs_frag, ip.cc:100-111), the cut into
+// fragments.  Like the reference's p.share(offset, can_send) + prepend, no
+// payload byte moves: a frame is a 20-byte header and two fragment records, so
+// the outputs feed ipv4_frames_desc / ipv4_fill_desc / a burst queue's mapped
+// form as they stand, and sccsum_gather packs them.  Stateless: any thread,
+// any stream of the data's device.
+//   tx_sender tx(host_address, hw.mtu, hw.tx_tso ? SCCSUM_SEND_TSO : 0);
+//   engine.sum_spans(l4, d_seeds, d_l4sum, nullptr, stream);          // pseudo-header seeds, fields zero
+//   tx.run(l4, d_dst, d_proto, d_id, d_l4sum, max_frames, max_bytes, out, tx.workspace(l4.n) sized d_ws, stream);
+//   engine.ipv4_fill_desc(out.desc, out.first, out.out_off, out.out_len, frames, mtu, SCCSUM_FILL_IP, ...);
+class tx_sender {
+    sccsum_send_opts _opts;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what a run writes (device arrays; sizes in <sccsum.h>, "Tx send")
+    struct outputs {
+        uint8_t* hdr = nullptr;               // 20 * max_frames bytes
+        sccsum_gather_desc* desc = nullptr;   // 2 * max_frames records
+        uint32_t* first = nullptr;            // max_frames + 1
+        uint64_t* out_off = nullptr;          // max_frames
+        uint32_t* out_len = nullptr;          // max_frames
+        uint32_t* dgram_first = nullptr;      // n + 1
+        uint8_t* status = nullptr;            // n
+        uint64_t* total = nullptr;            // 3: frames needed, bytes needed, datagrams emitted
+    };
+    struct plan_result {
+        uint32_t frames;     // 0: the datagram is refused (longer than 65515 bytes)
+        uint64_t out_bytes;  // its bytes in the packed layout
+    };
+
+    // src_host: ipv4::_host_address (host order); mtu: hw_features().mtu; flags: SCCSUM_SEND_*
+    // (SCCSUM_SEND_L4 is added by run() when it is given the L4 values)
+    tx_sender(uint32_t src_host, uint32_t mtu, uint32_t flags = 0) : _opts{src_host, mtu, flags} {}
+
+    const sccsum_send_opts& opts() const noexcept { return _opts; }
+
+    // host arithmetic for one datagram; throws on an MTU outside 68..65535 or unknown flags
+    static plan_result plan(const sccsum_send_opts& opts, uint32_t l4_len, uint8_t proto) {
+        plan_result r{0, 0};
+        check(sccsum_ipv4_send_plan(&opts, l4_len, proto, &r.frames, &r.out_bytes), "sccsum_ipv4_send_plan");
+        return r;
+    }
+    plan_result plan(uint32_t l4_len, uint8_t proto) const { return plan(_opts, l4_len, proto); }
+
+    // bytes of 16-byte aligned device scratch a run over n datagrams needs
+    static uint64_t workspace(uint64_t n) noexcept { return sccsum_ipv4_send_workspace(n); }
+
+    // l4: the datagrams (bytes is written only through d_l4sum's values); d_dst host-order
+    // addresses; d_id may be null (id 0); d_l4sum null, or the values to store in the UDP / TCP
+    // checksum fields before the cut.  Capacity is a prefix rule (out.total reports the need).
+    void run(const device_packet_batch& l4, const uint32_t* d_dst, const uint8_t* d_proto, const uint16_t* d_id,
+             const uint16_t* d_l4sum, uint64_t max_frames, uint64_t max_out_bytes, const outputs& out,
+             void* d_workspace, void* stream) const {
+        sccsum_send_opts o = _opts;
+        if (d_l4sum) o.flags |= SCCSUM_SEND_L4;
+        check(sccsum_ipv4_send(&o, const_cast<void*>(l4.bytes), l4.bytes_len, l4.off, l4.len, d_dst, d_proto, d_id,
+                               d_l4sum, l4.n, max_frames, max_out_bytes, out.hdr, out.desc, out.first, out.out_off,
+                               out.out_len, out.dgram_first, out.status, out.total, d_workspace, stream),
+              "sccsum_ipv4_send");
     }
 };
 

@@ -587,6 +587,134 @@ class Steer:
             pass
 
 
+@dataclass
+class SendResult:
+    """What sccsum_ipv4_send wrote (include/sccsum.h, "Tx send").  The per-frame
+    tensors have room for max_frames frames; frames_emitted() of them are
+    written.  (desc, first, out_off, out_len) sliced to the emitted frames are
+    the arguments of the *_desc calls; lists() returns them so."""
+    l4: PacketBatch          # the datagrams (the payload descriptors point into l4.data)
+    hdr: torch.Tensor        # uint8 [20 * max_frames]
+    desc: torch.Tensor       # uint8 [32 * max_frames]: two sccsum_gather_desc records per frame
+    first: torch.Tensor      # int32 [max_frames + 1]: 2f, and the closing entry
+    out_off: torch.Tensor    # int64 [max_frames]: the frame's position in the packed layout
+    out_len: torch.Tensor    # int32 [max_frames]
+    dgram_first: torch.Tensor  # int32 [n + 1]: datagram i's first frame
+    status: torch.Tensor     # uint8 [n]
+    total: torch.Tensor      # int64 [3]: frames needed, bytes needed, datagrams emitted
+    max_frames: int
+    max_out_bytes: int
+
+    def totals(self) -> tuple:
+        """(frames needed, layout bytes needed, datagrams emitted); synchronises."""
+        t = self.total.cpu().numpy()
+        return int(t[0]), int(t[1]), int(t[2])
+
+    def frames_emitted(self) -> int:
+        """Frames written (synchronises)."""
+        return int(self.dgram_first[-1].item()) & 0xFFFFFFFF
+
+    def lists(self) -> tuple:
+        """(desc, first, out_off, out_len, max_len) of the emitted frames, as
+        ipv4_frames_desc / ipv4_fill_desc / spans_desc take them; synchronises."""
+        e = self.frames_emitted()
+        ln = self.out_len[:e]
+        return self.desc[: 32 * e], self.first[: e + 1], self.out_off[:e], ln, (int(ln.max().item()) if e else 0)
+
+    def pack(self, stream=None) -> PacketBatch:
+        """The packed wire frames: sccsum_gather of every header and piece into
+        a new buffer (the one pass that moves payload bytes); synchronises to
+        size it."""
+        desc, _, off, ln, max_len = self.lists()
+        e = int(off.numel())
+        nbytes = int((off[-1] + ln[-1]).item()) if e else 0
+        data = _scratch(_round16(nbytes) or 16, self.l4.device, stream)
+        if e:
+            native.check(native.load().sccsum_gather(ctypes_ptr(desc), 2 * e, ctypes_ptr(data), _stream(stream)),
+                         "sccsum_gather")
+        return PacketBatch(data=data, off=off, length=ln, bytes_len=nbytes, max_len=max_len)
+
+
+def send_check(l4: PacketBatch, dst, proto, mtu, src_host, ids, l4sum, flags, max_frames, max_out_bytes) -> tuple:
+    """What ipv4_send refuses before any launch (the kernels trust the sizes);
+    returns (n, max_frames, max_out_bytes) with the default caps filled in:
+    every datagram needs at most ceil(len / (mtu - 20)) + 1 frames, so datagrams
+    that do not overlap need at most bytes_len // (mtu - 20) + 2 n."""
+    if not isinstance(l4, PacketBatch):
+        raise ValueError("l4: need a PacketBatch of L4 datagrams")
+    dev, n = l4.device, l4.n
+    if not 68 <= int(mtu) <= 65535:
+        raise ValueError(f"mtu: need 68..65535, got {mtu}")
+    if int(flags) & ~(native.SEND_TSO | native.SEND_UFO | native.SEND_NO_IP_CSUM | native.SEND_L4):
+        raise ValueError(f"flags: unknown bits in {int(flags):#x}")
+    if not 0 <= int(src_host) <= 0xFFFFFFFF:
+        raise ValueError("src_host: need a host-order IPv4 address, 0..2^32-1")
+    if n > 0xFFFFFFFF:
+        raise ValueError("l4: at most 2^32-1 datagrams")
+    for t, dtype, what in ((dst, torch.int32, "dst"), (proto, torch.uint8, "proto")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D {dtype} tensor of one entry per datagram")
+        _need(t, n, dtype, what, dev)
+    for t, what in ((ids, "ids"), (l4sum, "l4sum")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 1):
+            raise ValueError(f"{what}: need a 1-D int16 tensor of one entry per datagram")
+        _need(t, n, torch.int16, what, dev)
+    if bool(int(flags) & native.SEND_L4) != (l4sum is not None):
+        raise ValueError("l4sum: needed with SEND_L4, and only with it")
+    if max_frames is None:
+        max_frames = min(0x7FFFFFFF, 2 * n + l4.bytes_len // (int(mtu) - 20))
+    if max_out_bytes is None:
+        max_out_bytes = min(0xFFFFFFFF, l4.bytes_len + 20 * int(max_frames))
+    if not 0 <= int(max_frames) <= 0x7FFFFFFF:
+        raise ValueError("max_frames: need 0..2^31-1")
+    if not 0 <= int(max_out_bytes) <= 0xFFFFFFFF:
+        raise ValueError("max_out_bytes: need 0..2^32-1 (descriptor offsets are 32-bit)")
+    return n, int(max_frames), int(max_out_bytes)
+
+
+def ipv4_send(l4: PacketBatch, dst: torch.Tensor, proto: torch.Tensor, mtu: int, src_host: int,
+              ids: torch.Tensor | None = None, l4sum: torch.Tensor | None = None, flags: int = 0,
+              max_frames: int | None = None, max_out_bytes: int | None = None, stream=None) -> SendResult:
+    """sccsum_ipv4_send: ipv4::send (ip.cc:244-299) for a batch of L4 datagrams
+    on the device — every frame's IPv4 header and, past the MTU, the cut into
+    fragments, as header + payload fragment lists; no payload byte moves.
+
+        seeds = ...pseudo_seed(src, dst, proto, len) per datagram, fields zero
+        l4sum = spans(l4, seeds=seeds)
+        r = ipv4_send(l4, dst, proto, 1500, src, ids=ids, l4sum=l4sum, flags=native.SEND_L4)
+        frames = r.pack()                      # or ipv4_fill_desc(*r.lists()[:4], r.lists()[4]) where they lie
+
+    dst: int32 [n] (host-order addresses as uint32 values), proto: uint8 [n],
+    ids / l4sum: int16 [n].  Capacity is a prefix rule: r.totals() reports the
+    full need and how many datagrams were emitted."""
+    lib = native.load()
+    n, max_frames, max_out_bytes = send_check(l4, dst, proto, mtu, src_host, ids, l4sum, flags, max_frames,
+                                              max_out_bytes)
+    dev = l4.device
+    hdr = _scratch(20 * max(max_frames, 1), dev, stream)
+    desc = _scratch(32 * max(max_frames, 1), dev, stream)
+    first = _scratch(max_frames + 1, dev, stream, torch.int32)
+    out_off = _scratch(max(max_frames, 1), dev, stream, torch.int64)
+    out_len = _scratch(max(max_frames, 1), dev, stream, torch.int32)
+    dgram_first = _scratch(n + 1, dev, stream, torch.int32)
+    status = _scratch(max(n, 1), dev, stream, torch.uint8)
+    total = _scratch(3, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_ipv4_send_workspace(n)), dev, stream)
+    opts = native.SendOpts(int(src_host), int(mtu), int(flags))
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_ipv4_send(
+        ctypes.addressof(opts), ctypes_ptr(l4.data), l4.bytes_len, None if empty else ctypes_ptr(l4.off),
+        None if empty else ctypes_ptr(l4.length), None if empty else ctypes_ptr(dst),
+        None if empty else ctypes_ptr(proto), None if empty else _ptr(ids), None if empty else _ptr(l4sum), n,
+        max_frames, max_out_bytes, ctypes_ptr(hdr), ctypes_ptr(desc), ctypes_ptr(first), ctypes_ptr(out_off),
+        ctypes_ptr(out_len), ctypes_ptr(dgram_first), ctypes_ptr(status), ctypes_ptr(total), ctypes_ptr(ws),
+        _stream(stream))
+    native.check(code, "sccsum_ipv4_send")
+    return SendResult(l4=l4, hdr=hdr, desc=desc, first=first, out_off=out_off[:max_frames],
+                      out_len=out_len[:max_frames], dgram_first=dgram_first, status=status[:n], total=total,
+                      max_frames=max_frames, max_out_bytes=max_out_bytes)
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

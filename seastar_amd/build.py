@@ -9,6 +9,7 @@ from .native import LIB_PATH, PKG_DIR, REPO_DIR
 SOURCES = [
     os.path.join(PKG_DIR, "csrc", "sccsum.hip"),
     os.path.join(PKG_DIR, "csrc", "steer.hip"),
+    os.path.join(PKG_DIR, "csrc", "send.hip"),
     os.path.join(PKG_DIR, "csrc", "checksummer.cc"),
     os.path.join(PKG_DIR, "csrc", "pipeline.cc"),
     os.path.join(PKG_DIR, "csrc", "burst.cc"),

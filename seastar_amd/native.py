@@ -122,6 +122,12 @@ _PROTOS = {
     "sccsum_steer_dest": (_u32, [_vp, ctypes.c_int, _u32, _u32]),
     "sccsum_steer_build_reta": (ctypes.c_int, [_vp, _vp, _u32, _vp]),
     "sccsum_steer_tile_packets": (ctypes.c_int, []),
+    "sccsum_ipv4_send_plan": (ctypes.c_int, [_vp, _u32, ctypes.c_uint8, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
+    "sccsum_ipv4_send_workspace": (_u64, [_u64]),
+    "sccsum_ipv4_send": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sccsum_send_tile_datagrams": (ctypes.c_int, []),
+    "sccsum_send_emit_tile_frames": (ctypes.c_int, []),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -163,6 +169,18 @@ class SteerMap(ctypes.Structure):
     _fields_ = [("ncpu", ctypes.c_uint32), ("hw_queues", ctypes.c_uint32), ("table_bits", ctypes.c_uint32),
                 ("redir_size", ctypes.c_uint32), ("redir", ctypes.c_void_p), ("sw_reta", ctypes.c_void_p),
                 ("sw_reta_set", ctypes.c_void_p)]
+
+
+SEND_TSO = 0x01
+SEND_UFO = 0x02
+SEND_NO_IP_CSUM = 0x04
+SEND_L4 = 0x08
+SEND_L4_MAX = 65515  # the longest L4 datagram ipv4::send takes (ip_packet_len_max - 20)
+
+
+class SendOpts(ctypes.Structure):
+    """sccsum_send_opts: what ipv4::send takes from its interface (source address, MTU, offload flags)."""
+    _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class Fragment(ctypes.Structure):
