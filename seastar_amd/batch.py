@@ -148,7 +148,7 @@ def ipv4_frames(batch: PacketBatch, out2: torch.Tensor | None = None, status: to
         ctypes_ptr(out2), _ptr(status), n, batch.max_len, _stream(stream),
     )
     native.check(code, "sccsum_ipv4_frames")
-    return out2[: 2 * n].view(n, 2) if n else out2[:0].view(0, 2)
+    return _pairs(out2, n)
 
 
 def verify_frames(batch: PacketBatch, status: torch.Tensor, stream=None) -> torch.Tensor:
@@ -168,27 +168,45 @@ def verify_frames(batch: PacketBatch, status: torch.Tensor, stream=None) -> torc
     return status[:n]
 
 
-def _multi(fn, name, items, max_len, stream, width, with_seed):
-    lib = native.load()
-    if len(items) > native.MAX_BATCHES:
-        raise ValueError(f"at most {native.MAX_BATCHES} batches per launch")
-    arr = (native.Batch * max(len(items), 1))()
-    outs, rows = [], []
-    for i, it in enumerate(items):  # every batch checked before any address is taken
+def _pairs(out2: torch.Tensor, n: int) -> torch.Tensor:
+    """The [n, 2] view of a frames output (IPv4 header checksum, L4 checksum)."""
+    return out2[: 2 * n].view(n, 2)
+
+
+def _batch_array(items, width, seeds_ok, alloc_out, fill=False, stream=None):
+    """The native.Batch array of items [(PacketBatch, out | None, status | None[, seeds]), ...]
+    and their outputs.  width: out values per packet; seeds_ok: spans may carry
+    seeds; alloc_out: a missing out is allocated on `stream`, else it stands for
+    a verify-only batch, which needs its status; fill: every batch needs out."""
+    rows = []
+    for i, it in enumerate(items):  # every item is checked before any address is taken
         b, out, status = it[0], it[1], it[2]
         seeds = it[3] if len(it) > 3 else None
-        if seeds is not None and not with_seed:
-            raise ValueError(f"{name}: frames take no seeds")
+        if seeds is not None and not seeds_ok:
+            raise ValueError("frames take no seeds")
+        if fill and out is None:
+            raise ValueError(f"batch {i}: a fill step needs out2 (the values pass through it)")
+        if out is None and status is None and not alloc_out:
+            raise ValueError(f"batch {i}: give out, status or both")
         _need(out, width * b.n, torch.int16, f"batch {i} out", b.device)
-        _need(seeds, b.n, torch.int32, f"batch {i} seeds", b.device)
         _need(status, b.n, torch.uint8, f"batch {i} status", b.device)
+        _need(seeds, b.n, torch.int32, f"batch {i} seeds", b.device)
         rows.append((b, out, status, seeds))
+    arr = (native.Batch * max(len(rows), 1))()
+    outs = []
     for i, (b, out, status, seeds) in enumerate(rows):
-        if out is None:
+        if out is None and alloc_out:
             out = _scratch(max(width * b.n, width), b.device, stream, torch.int16)
         arr[i] = native.Batch(ctypes_ptr(b.data), b.bytes_len, ctypes_ptr(b.off), ctypes_ptr(b.length), _ptr(seeds),
-                              ctypes_ptr(out), _ptr(status), b.n)
+                              _ptr(out), _ptr(status), b.n)
         outs.append(out)
+    return arr, outs
+
+
+def _multi(fn, name, items, max_len, stream, width, with_seed):
+    if len(items) > native.MAX_BATCHES:
+        raise ValueError(f"at most {native.MAX_BATCHES} batches per launch")
+    arr, outs = _batch_array(items, width, with_seed, True, stream=stream)
     native.check(fn(ctypes.cast(arr, ctypes.c_void_p), len(items), max_len, _stream(stream)), name)
     return outs
 
@@ -198,7 +216,7 @@ def ipv4_frames_multi(items, stream=None) -> list:
     (<= 16) in ONE launch; returns the [n, 2] int16 outputs per batch."""
     ml = max((it[0].max_len for it in items), default=0)
     outs = _multi(native.load().sccsum_ipv4_frames_multi, "sccsum_ipv4_frames_multi", items, ml, stream, 2, False)
-    return [o[: 2 * it[0].n].view(it[0].n, 2) for o, it in zip(outs, items)]
+    return [_pairs(o, it[0].n) for o, it in zip(outs, items)]
 
 
 def prepare_ipv4_frames_multi(items):
@@ -208,16 +226,7 @@ def prepare_ipv4_frames_multi(items):
     lib = native.load()
     if not items or len(items) > native.MAX_BATCHES:
         raise ValueError(f"1..{native.MAX_BATCHES} batches per launch")
-    arr = (native.Batch * len(items))()
-    for i, (b, out, status) in enumerate(items):  # every batch checked before any address is taken
-        # out None: a verify-only batch (status bits only)
-        if out is None and status is None:
-            raise ValueError(f"batch {i}: give out2, status or both")
-        _need(out, 2 * b.n, torch.int16, f"batch {i} out2", b.device)
-        _need(status, b.n, torch.uint8, f"batch {i} status", b.device)
-    for i, (b, out, status) in enumerate(items):
-        arr[i] = native.Batch(ctypes_ptr(b.data), b.bytes_len, ctypes_ptr(b.off), ctypes_ptr(b.length), None,
-                              _ptr(out), _ptr(status), b.n)
+    arr, _ = _batch_array(items, 2, False, False)  # out None: a verify-only batch (status bits only)
     ml = max(it[0].max_len for it in items)
     fn, ptr, nb = lib.sccsum_ipv4_frames_multi, ctypes.cast(arr, ctypes.c_void_p), len(items)
 
@@ -278,7 +287,7 @@ def ipv4_fill(batch: PacketBatch, mode: int = native.FILL_IP | native.FILL_L4, o
         _ptr(vals), _ptr(status), n, batch.max_len, mode, _stream(stream),
     )
     native.check(code, "sccsum_ipv4_fill")
-    return None if out2 is None else out2[: 2 * n].view(n, 2)
+    return None if out2 is None else _pairs(out2, n)
 
 
 # The reference's default RSS key (Mellanox driver key, toeplitz.hh:52-58).
@@ -325,7 +334,7 @@ def ipv4_frames_rss(batch: PacketBatch, key: bytes = RSS_KEY_40, mode: int = nat
         ctypes_ptr(batch.data), batch.bytes_len, ctypes_ptr(batch.off), ctypes_ptr(batch.length), ctypes_ptr(out2),
         _ptr(status), n, batch.max_len, ctypes.addressof(kb), kl, mode, ctypes_ptr(hash_out), _stream(stream))
     native.check(code, "sccsum_ipv4_frames_rss")
-    return (out2[: 2 * n].view(n, 2) if n else out2[:0].view(0, 2)), hash_out[:n]
+    return _pairs(out2, n), hash_out[:n]
 
 
 def fragments(data: torch.Tensor, bytes_len: int, frag_off: torch.Tensor, frag_len: torch.Tensor,
@@ -406,7 +415,7 @@ def ipv4_frames_desc(desc: torch.Tensor, first: torch.Tensor, off: torch.Tensor,
     n = int(off.numel())
     out2 = _desc_call("sccsum_ipv4_frames_desc", desc, first, off, length, max_len, 2, None, stage, out2, status,
                       stream)
-    return out2[: 2 * n].view(n, 2) if n else out2[:0].view(0, 2)
+    return _pairs(out2, n)
 
 
 def ipv4_fill_desc(desc: torch.Tensor, first: torch.Tensor, off: torch.Tensor, length: torch.Tensor, max_len: int,
@@ -435,7 +444,7 @@ def ipv4_fill_desc(desc: torch.Tensor, first: torch.Tensor, off: torch.Tensor, l
     native.check(lib.sccsum_ipv4_fill_desc(_ptr(desc), ctypes_ptr(first), ctypes_ptr(off), ctypes_ptr(length),
                                            _ptr(stage), ctypes_ptr(out2), _ptr(status), n, max_len, mode,
                                            _stream(stream)), name)
-    return out2[: 2 * n].view(n, 2) if n else out2[:0].view(0, 2)
+    return _pairs(out2, n)
 
 
 def read_probe(buf: torch.Tensor, nbytes: int, sink: torch.Tensor | None = None, stream=None) -> torch.Tensor:
@@ -787,26 +796,8 @@ class Engine:
             raise ValueError(f"1..{native.ENGINE_MAX_BATCHES} batches per step")
         if fill_mode and not self.fill:
             raise ValueError("fill steps need Engine(..., fill=True)")
-        width = 2 if self.frames else 1
-        parts = []
-        for i, it in enumerate(items):  # every item is checked before any is built
-            b, out, status = it[0], it[1], it[2]
-            seeds = it[3] if len(it) > 3 else None
-            if self.frames and seeds is not None:
-                raise ValueError("frames take no seeds")
-            if fill_mode and out is None:
-                raise ValueError(f"batch {i}: a fill step needs out2 (the values pass through it)")
-            if out is None and status is None:
-                raise ValueError(f"batch {i}: give out, status or both")
-            _need(out, width * b.n, torch.int16, f"batch {i} out", b.device)
-            _need(status, b.n, torch.uint8, f"batch {i} status", b.device)
-            _need(seeds, b.n, torch.int32, f"batch {i} seeds", b.device)
-            parts.append((b, out, status, seeds))
-        arr = (native.Batch * len(items))()
-        for i, (b, out, status, seeds) in enumerate(parts):
-            arr[i] = native.Batch(ctypes_ptr(b.data), b.bytes_len, ctypes_ptr(b.off), ctypes_ptr(b.length),
-                                  _ptr(seeds), _ptr(out), _ptr(status), b.n)
-        return (arr, len(items), max(b.max_len for b, _, _, _ in parts), items, int(fill_mode))
+        arr, _ = _batch_array(items, 2 if self.frames else 1, not self.frames, False, fill=bool(fill_mode))
+        return (arr, len(items), max(it[0].max_len for it in items), items, int(fill_mode))
 
     def submit_prepared(self, prep, timeout_s: float = 10.0) -> int:
         arr, nb, ml, items, fill_mode = prep

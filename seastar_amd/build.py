@@ -1,25 +1,31 @@
-"""Build libsccsum.so in-tree with hipcc for gfx950."""
+"""Build libsccsum.so in-tree with hipcc for gfx950.
+
+SOURCES and headers() are the one list of what the library is made of: the
+A/B builds (tools/build_ab.sh) and the sanitizer builds (tests/test_sanitize.py)
+take them from here.
+"""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 
 from .native import LIB_PATH, PKG_DIR, REPO_DIR
 
-SOURCES = [
-    os.path.join(PKG_DIR, "csrc", "sccsum.hip"),
-    os.path.join(PKG_DIR, "csrc", "steer.hip"),
-    os.path.join(PKG_DIR, "csrc", "send.hip"),
-    os.path.join(PKG_DIR, "csrc", "checksummer.cc"),
-    os.path.join(PKG_DIR, "csrc", "pipeline.cc"),
-    os.path.join(PKG_DIR, "csrc", "burst.cc"),
-]
+CSRC = os.path.join(PKG_DIR, "csrc")
+SOURCES = [os.path.join(CSRC, f) for f in
+           ("sccsum.hip", "steer.hip", "send.hip", "checksummer.cc", "pipeline.cc", "burst.cc")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # The AMDGPU atomic optimizer rewrites the kernels' lane-0 atomics into
 # wave-wide ones whose result it reads back where they are issued; the flat
 # kernel's LATE form reads its tile claim back a tile later (sccsum.hip,
 # flat_body).  No kernel has an atomic it would help: each is one lane's.
 DEVICE_FLAGS = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
+
+
+def headers() -> list[str]:
+    """Every header the build reads: an edit to any of them makes the library stale."""
+    return sorted(glob.glob(os.path.join(REPO_DIR, "include", "sccsum*.h")) + glob.glob(os.path.join(CSRC, "*.h")))
 
 
 def hipcc_cmd(out: str = LIB_PATH) -> list[str]:
@@ -33,8 +39,7 @@ def hipcc_cmd(out: str = LIB_PATH) -> list[str]:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
-    headers = [os.path.join(REPO_DIR, "include", h) for h in ("sccsum.h", "sccsum_diag.h")]
-    newest = max(os.path.getmtime(p) for p in SOURCES + headers)
+    newest = max(os.path.getmtime(p) for p in SOURCES + headers())
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
         return LIB_PATH
     cmd = hipcc_cmd()
@@ -42,3 +47,4 @@ def build(force: bool = False, verbose: bool = True) -> str:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
     return LIB_PATH
+

@@ -34,11 +34,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
-#include <tuple>
-#include <type_traits>
-#include <utility>
 #include <vector>
 
+#include "host_launch.h"
 #include "sccsum.h"
 #include "sccsum_diag.h"
 
@@ -2563,35 +2561,30 @@ __global__ __launch_bounds__(kBlock) void read_probe_kernel(const u32x4* __restr
 // Everything a launch sizes or takes per device (CU count, counter pool)
 // comes from the device returned here, not from a second hipGetDevice.
 int launch_device(hipStream_t s, int* dev) {
-    int cur = 0;
-    hipError_t e = hipGetDevice(&cur);
+    int cur = -1, sd = -1;  // cur stays -1 only when hipGetDevice itself failed
+    const hipError_t e = host_launch::stream_devices(s, &cur, &sd);
+    if (cur >= kMaxDevices) return SCCSUM_ENODEV;  // (decided before the stream is asked)
     if (e != hipSuccess) return static_cast<int>(e);
-    if (cur < 0 || cur >= kMaxDevices) return SCCSUM_ENODEV;
-    if (s != nullptr) {
-        hipDevice_t sd = -1;
-        e = hipStreamGetDevice(s, &sd);
-        if (e != hipSuccess) return static_cast<int>(e);
-        if (sd != cur) return SCCSUM_EINVAL;
-    }
+    if (cur < 0) return SCCSUM_ENODEV;
+    if (sd != cur) return SCCSUM_EINVAL;
     *dev = cur;
     return SCCSUM_OK;
 }
 
-// Every launch goes through hipLaunchKernel, which returns THIS launch's
-// error: the caller's pending HIP error from an earlier, unrelated call is
-// neither dropped nor read as this launch failing.  The
-// arguments are converted to the kernel's own parameter types first.
-template <typename... P, typename... A>
-hipError_t launch_kernel(void (*k)(P...), dim3 grid, hipStream_t s, A&&... a) {
-    static_assert(sizeof...(P) == sizeof...(A), "argument count");
-    std::tuple<std::decay_t<P>...> t(static_cast<std::decay_t<P>>(std::forward<A>(a))...);
-    void* args[sizeof...(P)];
-    std::apply([&](auto&... x) {
-        size_t i = 0;
-        ((args[i++] = static_cast<void*>(&x)), ...);
-    }, t);
-    return hipLaunchKernel(reinterpret_cast<const void*>(k), grid, dim3(kBlock), args, 0, s);
-}
+// An entry point's stream as HIP's type and the device its launches run on
+// (launch_device); rc != SCCSUM_OK refuses the call.
+struct LaunchTarget {
+    hipStream_t s;
+    int dev = 0;
+    int rc;
+    explicit LaunchTarget(void* stream) : s(static_cast<hipStream_t>(stream)), rc(launch_device(s, &dev)) {}
+};
+
+using host_launch::launch_kernel;
+using host_launch::misaligned;
+
+// Blocks of kBlock threads for one thread per item.
+unsigned blocks_for(uint64_t n) { return static_cast<unsigned>((n + kBlock - 1) / kBlock); }
 
 std::atomic<int> g_cu_count[kMaxDevices];
 
@@ -2820,26 +2813,46 @@ int kernel_occupancy(const void* k) {
     return nb;
 }
 
-int flat_occupancy(FlatKernel k) { return kernel_occupancy(reinterpret_cast<const void*>(k)); }
+// Blocks of a kernel the device holds at once: its occupancy, capped by the
+// blocks-per-CU knob, on every CU.  Each launch rounds this its own way.
+template <class Kern>
+uint64_t resident_blocks(Kern kern, int dev) {
+    const int occ = kernel_occupancy(reinterpret_cast<const void*>(kern));
+    return static_cast<uint64_t>(cu_count(dev)) * (occ < t_knobs.blocks_per_cu ? occ : t_knobs.blocks_per_cu);
+}
+
+// Packets per tile of a flat launch or of an engine's summing step: about
+// tile_bytes of packets, at most tile_packets (<= 64, one per lane), and no
+// fewer tiles than there are wave slots (the caller's: a launch's grid cap, a
+// running engine's grid).  pbytes is packet_bytes() of the batches, so the
+// mean packet is floor(min(bytes, n * max_len) / n), which equals
+// min(floor(bytes / n), max_len): max_len caps the mean either way round.
+uint64_t packets_per_tile(uint64_t n_total, uint64_t pbytes, uint64_t slots, const Knobs& K) {
+    uint64_t bmax = static_cast<uint64_t>(K.tile_packets);
+    const uint64_t tb = static_cast<uint64_t>(K.tile_bytes);
+    if (tb && n_total) {
+        const uint64_t mean = pbytes / n_total ? pbytes / n_total : 1;
+        const uint64_t bb = tb / mean ? tb / mean : 1;
+        bmax = bb < bmax ? bb : bmax;
+    }
+    const uint64_t B = slots ? (n_total + slots - 1) / slots : 1;
+    return B < 1 ? 1 : (B > bmax ? bmax : B);
+}
+
+// The knobs every summing kernel takes as flag bits.
+uint32_t knob_flags(const Knobs& K) {
+    return static_cast<uint32_t>(K.out_policy) << kOutPolicyShift | (K.short_chunks ? 0u : kFlagFullChunks) |
+           static_cast<uint32_t>(K.run_align == 8 ? 2 : (K.run_align == 4 ? 1 : 0)) << kRunAlignShift;
+}
 
 // Q holds the queues (nq >= 1); tile0 is filled here from the tile size.
 // `dev` is the stream's device (launch_device).
 hipError_t launch_flat(FlatKernel kern, hipStream_t s, int dev, Queues& Q, uint64_t n_total, uint64_t bytes_total,
                        uint32_t flags, const RssParams& rss) {
     const Knobs& K = t_knobs;
-    const int occ = flat_occupancy(kern);
-    const uint64_t bpc = static_cast<uint64_t>(occ < K.blocks_per_cu ? occ : K.blocks_per_cu);
-    const uint64_t cap = static_cast<uint64_t>(cu_count(dev)) * bpc;
+    const uint64_t cap = resident_blocks(kern, dev);
     const uint64_t slots = cap * kWavesPerBlock;
-    uint64_t bmax = static_cast<uint64_t>(K.tile_packets);
-    const uint64_t tb = static_cast<uint64_t>(K.tile_bytes);
-    if (tb) {
-        const uint64_t mean = bytes_total / n_total ? bytes_total / n_total : 1;
-        const uint64_t bb = tb / mean ? tb / mean : 1;
-        bmax = bb < bmax ? bb : bmax;
-    }
-    uint64_t B = (n_total + slots - 1) / slots;
-    B = B < 1 ? 1 : (B > bmax ? bmax : B);
+    const uint64_t B = packets_per_tile(n_total, bytes_total, slots, K);
     Q.tile0[0] = 0;
     for (uint32_t q = 0; q < Q.nq; ++q) Q.tile0[q + 1] = Q.tile0[q] + (Q.n[q] + B - 1) / B;
     const uint64_t whole = Q.tile0[Q.nq];
@@ -2859,13 +2872,10 @@ hipError_t launch_flat(FlatKernel kern, hipStream_t s, int dev, Queues& Q, uint6
     // (small launches 0.5-0.9 us faster, profiles/r05_fill_one_pass.log)
     const bool dyn = K.dynamic && tiles > blocks * kWavesPerBlock;
     const HeadSlot H = dyn ? acquire_heads(s, dev) : HeadSlot{};
-    flags |= static_cast<uint32_t>(K.out_policy) << kOutPolicyShift;
-    if (!K.short_chunks) flags |= kFlagFullChunks;
-    flags |= static_cast<uint32_t>(K.run_align == 8 ? 2 : (K.run_align == 4 ? 1 : 0)) << kRunAlignShift;
     // the launch's own error decides whether the slot goes back: a kernel that
     // did not start never reports completion
-    const hipError_t e = launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), s, Q, static_cast<uint32_t>(B),
-                                       H.heads, H.done, H.ticket, flags, rss);
+    const hipError_t e = launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, Q,
+                                       static_cast<uint32_t>(B), H.heads, H.done, H.ticket, flags | knob_flags(K), rss);
     if (e != hipSuccess) release_unlaunched(H);
     return e;
 }
@@ -2876,7 +2886,8 @@ hipError_t launch_simple(int uc, hipStream_t s, int dev, const uint8_t* b, uint6
                          uint64_t n, uint32_t flags) {
     const dim3 g(grid_for(n, dev));
     auto go = [&](auto kern) {
-        return launch_kernel(kern, g, s, b, bytes_len, d_off, d_len, d_seed, d_out, d_status, n, flags);
+        return launch_kernel(kern, g, dim3(kBlock), 0, s, b, bytes_len, d_off, d_len, d_seed, d_out, d_status, n,
+                             flags);
     };
     switch (uc) {
         case 1: return go(csum_kernel<1, IPV4>);
@@ -2894,9 +2905,7 @@ hipError_t launch_rows(uint32_t max_len, hipStream_t s, int dev, const uint8_t* 
     // the grid is what the chip holds at once (a grid-stride kernel: blocks
     // that only start when others end would make the tail)
     auto go = [&](auto kern) {
-        const int occ = kernel_occupancy(reinterpret_cast<const void*>(kern));
-        const uint64_t bpc = static_cast<uint64_t>(occ < t_knobs.blocks_per_cu ? occ : t_knobs.blocks_per_cu);
-        const uint64_t cap = static_cast<uint64_t>(cu_count(dev)) * bpc;
+        const uint64_t cap = resident_blocks(kern, dev);
 #ifdef SCCSUM_AB_ROWS_TILE64
         uint64_t blocks = ((n + 63u) / 64u + kWavesPerBlock - 1) / kWavesPerBlock;  // A/B: 64-packet tiles
 #else
@@ -2908,8 +2917,8 @@ hipError_t launch_rows(uint32_t max_len, hipStream_t s, int dev, const uint8_t* 
 #endif
         blocks = blocks < cap ? blocks : cap;
         blocks = (blocks + 7u) & ~uint64_t(7);  // multiple of 8 for the XCD mapping
-        return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), s, b, bytes_len, d_off, d_len, d_seed, d_out,
-                             d_status, n, flags, rq);
+        return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, b, bytes_len, d_off, d_len,
+                             d_seed, d_out, d_status, n, flags, rq);
     };
     if (units <= 32) return go(csum_row_kernel<2, IPV4, MQ, FILL>);
     if (units <= 64) return go(csum_row_kernel<4, IPV4, MQ, FILL>);
@@ -2967,9 +2976,25 @@ bool batch_ok(const void* d_bytes, const uint64_t* d_off, const uint32_t* d_len,
     // reference's verify only tests get() != 0, ip.cc:121-127, tcp.hh:876-883)
     const bool out_optional = (flags & kFillFlags) || (IPV4 && d_status != nullptr);
     if (!d_bytes || !d_off || !d_len || (!d_out && !out_optional)) return false;
-    return !((reinterpret_cast<uintptr_t>(d_bytes) & 15u) || (reinterpret_cast<uintptr_t>(d_off) & 7u) ||
-             (reinterpret_cast<uintptr_t>(d_len) & 3u) || (reinterpret_cast<uintptr_t>(d_seed) & 3u) ||
-             (reinterpret_cast<uintptr_t>(d_out) & (IPV4 ? 3u : 1u)));
+    return !(misaligned(d_bytes, 16) || misaligned(d_off, 8) || misaligned(d_len, 4) || misaligned(d_seed, 4) ||
+             misaligned(d_out, IPV4 ? 4 : 2));
+}
+
+// The next queue of a launch's table (Queues or RowQueues) from a batch; each
+// table keeps the packet counts its own way.
+void put_count(Queues& Q, uint32_t q, uint64_t n) { Q.n[q] = n; }
+void put_count(RowQueues& Q, uint32_t q, uint64_t n) { Q.first[q + 1] = Q.first[q] + n; }
+template <class Table>
+void add_queue(Table& Q, const sccsum_batch& x) {
+    const uint32_t q = Q.nq++;
+    Q.bytes[q] = static_cast<const uint8_t*>(x.d_bytes);
+    Q.bytes_len[q] = x.bytes_len;
+    Q.off[q] = x.d_off;
+    Q.len[q] = x.d_len;
+    Q.seed[q] = x.d_seed;
+    Q.out[q] = static_cast<uint16_t*>(x.d_out);
+    Q.status[q] = x.d_status;
+    put_count(Q, q, x.n);
 }
 
 // default: the flat kernel, all loads nontemporal — 16 units per lane per
@@ -3014,9 +3039,8 @@ int launch(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const
            void* stream, uint32_t flags = 0, const RssParams& rss = kNoRss) {
     if (n == 0) return SCCSUM_OK;
     if (!batch_ok<IPV4>(d_bytes, d_off, d_len, d_seed, d_out, d_status, flags)) return SCCSUM_EINVAL;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     int variant = pick_variant(n, bytes_len, flags, max_len);
     // a small single-batch launch runs the row kernel whatever the layout:
     // four packets per wave in one row step reach the results sooner than the
@@ -3032,28 +3056,20 @@ int launch(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const
     const uint8_t* b = static_cast<const uint8_t*>(d_bytes);
     if (variant == 1 || variant == 2) {
         hipError_t e = variant == 1
-                           ? launch_simple<IPV4>(units_class(max_len), s, dev, b, bytes_len, d_off, d_len, d_seed,
+                           ? launch_simple<IPV4>(units_class(max_len), T.s, T.dev, b, bytes_len, d_off, d_len, d_seed,
                                                  d_out, d_status, n, flags)
-                           : launch_rows<IPV4>(max_len, s, dev, b, bytes_len, d_off, d_len, d_seed, d_out, d_status,
+                           : launch_rows<IPV4>(max_len, T.s, T.dev, b, bytes_len, d_off, d_len, d_seed, d_out, d_status,
                                                n, flags);
         if (e == hipSuccess && IPV4 && rss.hash != nullptr) {  // RSS is fused only in the flat kernel
-            e = launch_kernel(rss_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), s, b, bytes_len,
-                              d_off, d_len, nullptr, n, rss);
+            e = launch_kernel(rss_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, T.s, b, bytes_len, d_off, d_len,
+                              nullptr, n, rss);
         }
         return static_cast<int>(e);
     } else {
         Queues Q{};
-        Q.nq = 1;
-        Q.bytes[0] = b;
-        Q.bytes_len[0] = bytes_len;
-        Q.off[0] = d_off;
-        Q.len[0] = d_len;
-        Q.seed[0] = d_seed;
-        Q.out[0] = d_out;
-        Q.status[0] = d_status;
-        Q.n[0] = n;
+        add_queue(Q, sccsum_batch{d_bytes, bytes_len, d_off, d_len, d_seed, d_out, d_status, n});
         return static_cast<int>(
-            launch_flat_variant<IPV4>(variant, s, dev, Q, n, packet_bytes(n, bytes_len, max_len), flags, rss));
+            launch_flat_variant<IPV4>(variant, T.s, T.dev, Q, n, packet_bytes(n, bytes_len, max_len), flags, rss));
     }
 }
 
@@ -3072,9 +3088,8 @@ int launch_multi(const sccsum_batch* batches, uint32_t nbatch, uint32_t max_len,
         bytes_total += x.n ? x.bytes_len : 0;
     }
     if (n_total == 0) return SCCSUM_OK;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     const int variant = pick_variant(n_total, bytes_total, 0, max_len);
     // a small multi launch runs the row kernel over all its batches at once
     // (as a small single-batch launch does, launch(): 16 x 32 frames 6.3 ->
@@ -3082,19 +3097,9 @@ int launch_multi(const sccsum_batch* batches, uint32_t nbatch, uint32_t max_len,
     if (t_knobs.variant == 0 && n_total <= kSmallRowsMax) {
         RowQueues rq{};
         for (uint32_t i = 0; i < nbatch; ++i) {
-            const sccsum_batch& x = batches[i];
-            if (!x.n) continue;
-            const uint32_t q = rq.nq++;
-            rq.first[q + 1] = rq.first[q] + x.n;
-            rq.bytes[q] = static_cast<const uint8_t*>(x.d_bytes);
-            rq.bytes_len[q] = x.bytes_len;
-            rq.off[q] = x.d_off;
-            rq.len[q] = x.d_len;
-            rq.seed[q] = x.d_seed;
-            rq.out[q] = static_cast<uint16_t*>(x.d_out);
-            rq.status[q] = x.d_status;
+            if (batches[i].n) add_queue(rq, batches[i]);
         }
-        return static_cast<int>(launch_rows<IPV4, true>(max_len, s, dev, nullptr, 0, nullptr, nullptr, nullptr,
+        return static_cast<int>(launch_rows<IPV4, true>(max_len, T.s, T.dev, nullptr, 0, nullptr, nullptr, nullptr,
                                                         nullptr, nullptr, n_total, 0, rq));
     }
     if (variant == 1 || variant == 2) {  // the per-packet kernels take one batch per launch
@@ -3104,29 +3109,19 @@ int launch_multi(const sccsum_batch* batches, uint32_t nbatch, uint32_t max_len,
             const auto* b = static_cast<const uint8_t*>(x.d_bytes);
             auto* o = static_cast<uint16_t*>(x.d_out);
             const hipError_t e =
-                variant == 1 ? launch_simple<IPV4>(units_class(max_len), s, dev, b, x.bytes_len, x.d_off, x.d_len,
-                                                   x.d_seed, o, x.d_status, x.n, 0)
-                             : launch_rows<IPV4>(max_len, s, dev, b, x.bytes_len, x.d_off, x.d_len, x.d_seed, o,
-                                                 x.d_status, x.n, 0);
+                variant == 1 ? launch_simple<IPV4>(units_class(max_len), T.s, T.dev, b, x.bytes_len, x.d_off,
+                                                   x.d_len, x.d_seed, o, x.d_status, x.n, 0)
+                             : launch_rows<IPV4>(max_len, T.s, T.dev, b, x.bytes_len, x.d_off, x.d_len, x.d_seed,
+                                                 o, x.d_status, x.n, 0);
             if (e != hipSuccess) return static_cast<int>(e);
         }
         return SCCSUM_OK;
     }
     Queues Q{};
     for (uint32_t i = 0; i < nbatch; ++i) {
-        const sccsum_batch& x = batches[i];
-        if (!x.n) continue;
-        const uint32_t q = Q.nq++;
-        Q.bytes[q] = static_cast<const uint8_t*>(x.d_bytes);
-        Q.bytes_len[q] = x.bytes_len;
-        Q.off[q] = x.d_off;
-        Q.len[q] = x.d_len;
-        Q.seed[q] = IPV4 ? nullptr : x.d_seed;
-        Q.out[q] = static_cast<uint16_t*>(x.d_out);
-        Q.status[q] = x.d_status;
-        Q.n[q] = x.n;
+        if (batches[i].n) add_queue(Q, batches[i]);  // (a frames batch's d_seed is NULL: checked above)
     }
-    return static_cast<int>(launch_flat_variant<IPV4>(variant, s, dev, Q, n_total,
+    return static_cast<int>(launch_flat_variant<IPV4>(variant, T.s, T.dev, Q, n_total,
                                                       packet_bytes(n_total, bytes_total, max_len), 0, kNoRss));
 }
 
@@ -3493,36 +3488,6 @@ __global__ __launch_bounds__(kBlock) void csum_desc_kernel(
     }
 }
 
-template <bool IPV4>
-int launch_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
-                const uint32_t* d_len, const uint32_t* d_seed, const void* d_stage, uint16_t* d_out, uint8_t* d_status,
-                uint64_t n, uint32_t max_len, void* stream) {
-    if (n == 0) return SCCSUM_OK;
-    // d_desc may be NULL (an rx burst of empty packets has no fragments): the
-    // kernel then gives every packet zero fragments, so an empty one sums to
-    // the empty sum and a non-empty one is SCCSUM_ST_RANGE (VERDICT r05 #6)
-    if (!d_first || !d_off || !d_len || !d_out || (reinterpret_cast<uintptr_t>(d_desc) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_first) & 3u) || (reinterpret_cast<uintptr_t>(d_off) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_len) & 3u) || (reinterpret_cast<uintptr_t>(d_seed) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_out) & (IPV4 ? 3u : 1u))) {
-        return SCCSUM_EINVAL;
-    }
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = launch_device(s, &dev); rc != SCCSUM_OK) return rc;
-    const auto* st = static_cast<const uint8_t*>(d_stage);
-    const dim3 g(grid_for(n, dev));
-    auto go = [&](auto kern) {
-        return static_cast<int>(launch_kernel(kern, g, s, d_desc, d_first, d_off, d_len, d_seed, st, d_out, d_status,
-                                              n, 0u));
-    };
-    switch (units_class(max_len)) {
-        case 1: return go(csum_desc_kernel<1, IPV4>);
-        case 2: return go(csum_desc_kernel<2, IPV4>);
-        default: return go(csum_desc_kernel<4, IPV4>);
-    }
-}
-
 // sccsum_ipv4_fill's mode rules (sccsum.h): at least one bit, only known bits,
 // FILL_L4_PSEUDO excludes FILL_L4 and FILL_ICMP_ECHO, FILL_TSO needs FILL_L4_PSEUDO.
 bool fill_mode_ok(uint32_t mode) {
@@ -3533,48 +3498,58 @@ bool fill_mode_ok(uint32_t mode) {
            !((mode & SCCSUM_FILL_ICMP_ECHO) && (mode & SCCSUM_FILL_L4_PSEUDO));
 }
 
-// The fill form of launch_desc: one launch, the kernel stores the fields
-// through the descriptors' own addresses (d_stage for src == NULL fragments).
-int launch_desc_fill(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
-                     const uint32_t* d_len, void* d_stage, uint16_t* d_out2, uint8_t* d_status, uint64_t n,
-                     uint32_t max_len, uint32_t mode, void* stream) {
-    if (!fill_mode_ok(mode)) return SCCSUM_EINVAL;
+// The public fill mode's summing bits as the flat, row and engine kernels take them.
+uint32_t fill_flags(uint32_t mode) {
+    return ((mode & SCCSUM_FILL_L4) ? kFlagFillL4 : 0u) | ((mode & SCCSUM_FILL_ICMP_ECHO) ? kFlagFillIcmp : 0u) |
+           ((mode & SCCSUM_FILL_IP) ? kFlagFillIp : 0u);
+}
+
+// FILL: one launch, the kernel stores the fields through the descriptors' own
+// addresses (d_stage for src == NULL fragments); `mode` is the SCCSUM_FILL_*
+// mode, checked before n == 0, and d_out may be NULL.  Else mode is 0.
+template <bool IPV4, bool FILL = false>
+int launch_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
+                const uint32_t* d_len, const uint32_t* d_seed, const void* d_stage, uint16_t* d_out, uint8_t* d_status,
+                uint64_t n, uint32_t max_len, uint32_t mode, void* stream) {
+    if (FILL && !fill_mode_ok(mode)) return SCCSUM_EINVAL;
     if (n == 0) return SCCSUM_OK;
-    if (!d_first || !d_off || !d_len || (reinterpret_cast<uintptr_t>(d_desc) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_first) & 3u) || (reinterpret_cast<uintptr_t>(d_off) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_len) & 3u) || (reinterpret_cast<uintptr_t>(d_out2) & 3u)) {
+    // d_desc may be NULL (an rx burst of empty packets has no fragments): the
+    // kernel then gives every packet zero fragments, so an empty one sums to
+    // the empty sum and a non-empty one is SCCSUM_ST_RANGE (VERDICT r05 #6)
+    if (!d_first || !d_off || !d_len || (!FILL && !d_out) || misaligned(d_desc, 8) || misaligned(d_first, 4) ||
+        misaligned(d_off, 8) || misaligned(d_len, 4) || misaligned(d_seed, 4) || misaligned(d_out, IPV4 ? 4 : 2)) {
         return SCCSUM_EINVAL;
     }
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = launch_device(s, &dev); rc != SCCSUM_OK) return rc;
-    const auto* st = static_cast<const uint8_t*>(d_stage);
-    const dim3 g(grid_for(n, dev));
+    const LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     auto go = [&](auto kern) {
-        return static_cast<int>(launch_kernel(kern, g, s, d_desc, d_first, d_off, d_len,
-                                              static_cast<const uint32_t*>(nullptr), st, d_out2, d_status, n, mode));
+        return static_cast<int>(launch_kernel(kern, dim3(grid_for(n, T.dev)), dim3(kBlock), 0, T.s, d_desc, d_first,
+                                              d_off, d_len, d_seed, static_cast<const uint8_t*>(d_stage), d_out,
+                                              d_status, n, mode));
     };
-    // the header-only modes read no payload: one unit per lane is plenty
-    const bool sums = (mode & (SCCSUM_FILL_L4 | SCCSUM_FILL_ICMP_ECHO)) != 0;
+    // the header-only fill modes read no payload: one unit per lane is plenty
+    const bool sums = !FILL || (mode & (SCCSUM_FILL_L4 | SCCSUM_FILL_ICMP_ECHO)) != 0;
     switch (sums ? units_class(max_len) : 1) {
-        case 1: return go(csum_desc_kernel<1, true, true>);
-        case 2: return go(csum_desc_kernel<2, true, true>);
-        default: return go(csum_desc_kernel<4, true, true>);
+        case 1: return go(csum_desc_kernel<1, IPV4, FILL>);
+        case 2: return go(csum_desc_kernel<2, IPV4, FILL>);
+        default: return go(csum_desc_kernel<4, IPV4, FILL>);
     }
 }
+// (instantiated here: the fill kernels keep their place in the code object)
+template int launch_desc<true, true>(const sccsum_gather_desc*, const uint32_t*, const uint64_t*, const uint32_t*,
+                                     const uint32_t*, const void*, uint16_t*, uint8_t*, uint64_t, uint32_t, uint32_t,
+                                     void*);
 
 // Engine launch: the grid is what the chip holds at once (every wave's tiles
 // come from the claim counters, so no block waits for another to finish).
 template <bool IPV4, bool FILL = false>
 hipError_t launch_engine(hipStream_t s, int dev, const EngineArgs& E, uint32_t flags, uint64_t* waves) {
     auto kern = csum_engine_kernel<16, IPV4, FILL>;
-    const int occ = kernel_occupancy(reinterpret_cast<const void*>(kern));
-    const uint64_t bpc = static_cast<uint64_t>(occ < t_knobs.blocks_per_cu ? occ : t_knobs.blocks_per_cu);
-    uint64_t blocks = static_cast<uint64_t>(cu_count(dev)) * bpc;
-    blocks = blocks & ~uint64_t(15);  // multiple of 16: XCD mapping, waves divide into kGroups
+    // a multiple of 16: XCD mapping, waves divide into kGroups
+    uint64_t blocks = resident_blocks(kern, dev) & ~uint64_t(15);
     if (blocks == 0) blocks = 16;
     *waves = blocks * kWavesPerBlock;
-    return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), s, E, flags);
+    return launch_kernel(kern, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, E, flags);
 }
 
 }  // namespace
@@ -3756,29 +3731,20 @@ bool engine_room(sccsum_engine* e, uint32_t k, uint64_t* need) {
     return false;
 }
 
-// Packets per tile of a summing step, as a launch picks them (launch_flat):
-// about tile_bytes of packets, at most 64, and no fewer tiles than the grid
-// has waves.  The mean packet is the batches' bytes over their packets, capped
-// by max_len when the caller gives it: a batch that is a slice of a larger
-// buffer (bytes_len covers the whole buffer) would otherwise look sparse and
-// get tiles of a packet or two.  (The knobs are the submitting thread's.)
+// Packets per tile of a summing step, the function a launch picks them with
+// (packets_per_tile), over the running grid's waves.  The mean packet is the
+// batches' bytes over their packets, capped by max_len when the caller gives
+// it (packet_bytes): a batch that is a slice of a larger buffer (bytes_len
+// covers the whole buffer) would otherwise look sparse and get tiles of a
+// packet or two.  (The knobs are the submitting thread's.)
 uint64_t engine_tile(const sccsum_engine* e, const sccsum_batch* batches, uint32_t nbatch, uint32_t max_len) {
     uint64_t n_total = 0, bytes_total = 0;
     for (uint32_t i = 0; i < nbatch; ++i) {
         n_total += batches[i].n;
         bytes_total += batches[i].n ? batches[i].bytes_len : 0;
     }
-    const sccsum::Knobs& K = sccsum::t_knobs;
-    uint64_t bmax = static_cast<uint64_t>(K.tile_packets);
-    if (K.tile_bytes && n_total) {
-        uint64_t mean = bytes_total / n_total ? bytes_total / n_total : 1;
-        if (max_len && mean > max_len) mean = max_len;
-        const uint64_t tb = static_cast<uint64_t>(K.tile_bytes);
-        const uint64_t bb = tb / mean ? tb / mean : 1;
-        bmax = bb < bmax ? bb : bmax;
-    }
-    uint64_t B = e->waves ? (n_total + e->waves - 1) / e->waves : 1;
-    return B < 1 ? 1 : (B > bmax ? bmax : B);
+    return sccsum::packets_per_tile(n_total, sccsum::packet_bytes(n_total, bytes_total, max_len), e->waves,
+                                    sccsum::t_knobs);
 }
 
 // Write one step's descriptor over checked batches (nbatch 0: an empty step,
@@ -3984,9 +3950,10 @@ int sccsum_engine_start(sccsum_engine* e, void* stream) {
     if (!e) return SCCSUM_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (e->running) return SCCSUM_EINVAL;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = sccsum::launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const sccsum::LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
+    const hipStream_t s = T.s;
+    const int dev = T.dev;
     if (dev != e->device) return SCCSUM_EINVAL;
     {
         std::lock_guard<std::mutex> gl(g_live_mu);
@@ -4013,10 +3980,7 @@ int sccsum_engine_start(sccsum_engine* e, void* stream) {
         return static_cast<int>(r);
     }
     const sccsum::Knobs& K = sccsum::t_knobs;
-    uint32_t flags = static_cast<uint32_t>(K.out_policy) << sccsum::kOutPolicyShift;
-    if (K.engine_wt) flags |= sccsum::kFlagEngineWT;
-    if (!K.short_chunks) flags |= sccsum::kFlagFullChunks;
-    flags |= static_cast<uint32_t>(K.run_align == 8 ? 2 : (K.run_align == 4 ? 1 : 0)) << sccsum::kRunAlignShift;
+    const uint32_t flags = sccsum::knob_flags(K) | (K.engine_wt ? sccsum::kFlagEngineWT : 0u);
     // the engine's idle limit, unless this thread's diagnostic knob overrides it
     e->args.idle_ticks = K.engine_idle_ms > 0 ? static_cast<uint64_t>(K.engine_idle_ms) * 100000ull : e->idle_ticks;
     r = e->fill ? sccsum::launch_engine<true, true>(s, dev, e->args, flags, &e->waves)
@@ -4070,10 +4034,7 @@ int sccsum_engine_submit_fill(sccsum_engine* e, const sccsum_batch* batches, uin
     // step, no wait on the generate step: a store step's waves hold the next
     // fill's tiles while they wait, which chained small fills one after another)
     const bool single = n_total <= sccsum::t_knobs.fill_single_max;
-    const uint64_t kflags = ((mode & SCCSUM_FILL_L4) ? sccsum::kFlagFillL4 : 0u) |
-                            ((mode & SCCSUM_FILL_ICMP_ECHO) ? sccsum::kFlagFillIcmp : 0u) |
-                            ((mode & SCCSUM_FILL_IP) ? sccsum::kFlagFillIp : 0u) |
-                            (single ? sccsum::kFlagFillNow : 0u);
+    const uint64_t kflags = sccsum::fill_flags(mode) | (single ? sccsum::kFlagFillNow : 0u);
     const uint64_t gen_kind = sccsum::kStepFillGen | (kflags << 8) | (uint64_t(mode) << 16);
     if (single) {
         return engine_publish(e, 1, timeout_ns, [&] {
@@ -4215,26 +4176,23 @@ int sccsum_ipv4_frames_multi(const sccsum_batch* batches, uint32_t nbatch, uint3
 
 static int rss_args_ok(const uint8_t* key, uint32_t key_len, int mode, const uint32_t* d_hash) {
     return key && key_len >= 4 && (mode == SCCSUM_RSS_DISPATCH || mode == SCCSUM_RSS_REASSEMBLED) && d_hash &&
-           !(reinterpret_cast<uintptr_t>(d_hash) & 3u);
+           !sccsum::misaligned(d_hash, 4);
 }
 
 int sccsum_ipv4_rss(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
                     const uint8_t* key, uint32_t key_len, int mode, uint32_t* d_hash, uint8_t* d_status, uint64_t n,
                     void* stream) {
     if (n == 0) return SCCSUM_OK;
-    if (!rss_args_ok(key, key_len, mode, d_hash) || !d_bytes || !d_off || !d_len ||
-        (reinterpret_cast<uintptr_t>(d_bytes) & 15u) || (reinterpret_cast<uintptr_t>(d_off) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_len) & 3u)) {
+    if (!rss_args_ok(key, key_len, mode, d_hash) || !d_bytes || !d_off || !d_len || sccsum::misaligned(d_bytes, 16) ||
+        sccsum::misaligned(d_off, 8) || sccsum::misaligned(d_len, 4)) {
         return SCCSUM_EINVAL;
     }
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = sccsum::launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const sccsum::LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     const sccsum::RssParams P = sccsum::make_rss(key, key_len, static_cast<uint32_t>(mode), d_hash);
-    return static_cast<int>(sccsum::launch_kernel(sccsum::rss_kernel,
-                                                  dim3(static_cast<unsigned>((n + sccsum::kBlock - 1) / sccsum::kBlock)),
-                                                  s, static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len,
-                                                  d_status, n, P));
+    return static_cast<int>(sccsum::launch_kernel(sccsum::rss_kernel, dim3(sccsum::blocks_for(n)),
+                                                  dim3(sccsum::kBlock), 0, T.s, static_cast<const uint8_t*>(d_bytes),
+                                                  bytes_len, d_off, d_len, d_status, n, P));
 }
 
 int sccsum_ipv4_frames_rss(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
@@ -4249,34 +4207,34 @@ int sccsum_ipv4_frames_rss(const void* d_bytes, uint64_t bytes_len, const uint64
 
 int sccsum_gather(const sccsum_gather_desc* d_desc, uint64_t n, void* d_dst, void* stream) {
     if (n == 0) return SCCSUM_OK;
-    if (!d_desc || !d_dst || (reinterpret_cast<uintptr_t>(d_desc) & 7u)) return SCCSUM_EINVAL;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = sccsum::launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    if (!d_desc || !d_dst || sccsum::misaligned(d_desc, 8)) return SCCSUM_EINVAL;
+    const sccsum::LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     const uint64_t blocks = std::min<uint64_t>((n + 3) / 4, 65536);
-    return static_cast<int>(sccsum::launch_kernel(sccsum::gather_kernel, dim3(static_cast<unsigned>(blocks)), s, d_desc,
-                                                  n, static_cast<uint8_t*>(d_dst)));
+    return static_cast<int>(sccsum::launch_kernel(sccsum::gather_kernel, dim3(static_cast<unsigned>(blocks)),
+                                                  dim3(sccsum::kBlock), 0, T.s, d_desc, n,
+                                                  static_cast<uint8_t*>(d_dst)));
 }
 
 int sccsum_spans_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                       const uint32_t* d_len, const uint32_t* d_seed, const void* d_stage, uint16_t* d_out,
                       uint8_t* d_status, uint64_t n, uint32_t max_len, void* stream) {
-    return sccsum::launch_desc<false>(d_desc, d_first, d_off, d_len, d_seed, d_stage, d_out, d_status, n, max_len,
+    return sccsum::launch_desc<false>(d_desc, d_first, d_off, d_len, d_seed, d_stage, d_out, d_status, n, max_len, 0,
                                       stream);
 }
 
 int sccsum_ipv4_frames_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                             const uint32_t* d_len, const void* d_stage, uint16_t* d_out2, uint8_t* d_status,
                             uint64_t n, uint32_t max_len, void* stream) {
-    return sccsum::launch_desc<true>(d_desc, d_first, d_off, d_len, nullptr, d_stage, d_out2, d_status, n, max_len,
+    return sccsum::launch_desc<true>(d_desc, d_first, d_off, d_len, nullptr, d_stage, d_out2, d_status, n, max_len, 0,
                                      stream);
 }
 
 int sccsum_ipv4_fill_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                           const uint32_t* d_len, void* d_stage, uint16_t* d_out2, uint8_t* d_status, uint64_t n,
                           uint32_t max_len, uint32_t mode, void* stream) {
-    return sccsum::launch_desc_fill(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len, mode,
-                                    stream);
+    return sccsum::launch_desc<true, true>(d_desc, d_first, d_off, d_len, nullptr, d_stage, d_out2, d_status, n,
+                                           max_len, mode, stream);
 }
 
 uint64_t sccsum_fragments_workspace(uint64_t nfrag) { return ((2 * nfrag + 15) & ~uint64_t(15)) + nfrag + 16; }
@@ -4286,13 +4244,12 @@ int sccsum_fragments(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_
                      uint8_t* d_status, uint64_t n, uint32_t max_frag_len, void* d_workspace, void* stream) {
     if (n == 0) return SCCSUM_OK;
     if (!d_pkt_first || !d_out || (nfrag && (!d_workspace || !d_frag_off || !d_frag_len)) ||
-        (reinterpret_cast<uintptr_t>(d_workspace) & 15u) || (reinterpret_cast<uintptr_t>(d_pkt_first) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_seed) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & 1u)) {
+        sccsum::misaligned(d_workspace, 16) || sccsum::misaligned(d_pkt_first, 4) || sccsum::misaligned(d_seed, 4) ||
+        sccsum::misaligned(d_out, 2)) {
         return SCCSUM_EINVAL;
     }
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = sccsum::launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const sccsum::LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     auto* raw = static_cast<uint16_t*>(d_workspace);
     auto* raw_st = static_cast<uint8_t*>(d_workspace) + ((2 * nfrag + 15) & ~uint64_t(15));
     if (nfrag) {
@@ -4300,9 +4257,9 @@ int sccsum_fragments(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_
                                              max_frag_len, stream, sccsum::kFlagRaw);
         if (rc != SCCSUM_OK) return rc;
     }
-    const unsigned grid = static_cast<unsigned>((n + sccsum::kBlock - 1) / sccsum::kBlock);
-    return static_cast<int>(sccsum::launch_kernel(sccsum::frag_combine_kernel, dim3(grid), s, d_frag_len, nfrag,
-                                                  d_pkt_first, raw, raw_st, d_seed, d_out, d_status, n));
+    return static_cast<int>(sccsum::launch_kernel(sccsum::frag_combine_kernel, dim3(sccsum::blocks_for(n)),
+                                                  dim3(sccsum::kBlock), 0, T.s, d_frag_len, nfrag, d_pkt_first, raw,
+                                                  raw_st, d_seed, d_out, d_status, n));
 }
 
 int sccsum_ipv4_fill(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
@@ -4312,26 +4269,23 @@ int sccsum_ipv4_fill(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, c
     if (n == 0) return SCCSUM_OK;
     const bool two_pass = (mode & (SCCSUM_FILL_L4 | SCCSUM_FILL_ICMP_ECHO)) != 0;
     if (two_pass ? !sccsum::batch_ok<true>(d_bytes, d_off, d_len, nullptr, d_out2, d_status, sccsum::kFlagFillL4)
-                 : (!d_bytes || !d_off || !d_len || (reinterpret_cast<uintptr_t>(d_off) & 7u) ||
-                    (reinterpret_cast<uintptr_t>(d_len) & 3u) || (reinterpret_cast<uintptr_t>(d_out2) & 3u))) {
+                 : (!d_bytes || !d_off || !d_len || sccsum::misaligned(d_off, 8) || sccsum::misaligned(d_len, 4) ||
+                    sccsum::misaligned(d_out2, 4))) {
         return SCCSUM_EINVAL;  // (before any allocation)
     }
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = sccsum::launch_device(s, &dev); rc != SCCSUM_OK) return rc;
+    const sccsum::LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
     if (two_pass && n <= sccsum::t_knobs.fill_single_max) {
         // a small fill in one pass: the generate tiles store the fields
         // themselves (kFlagFillNow; d_out2 stays optional, nothing to hand over)
-        const uint32_t flags = ((mode & SCCSUM_FILL_L4) ? sccsum::kFlagFillL4 : 0u) |
-                               ((mode & SCCSUM_FILL_ICMP_ECHO) ? sccsum::kFlagFillIcmp : 0u) |
-                               ((mode & SCCSUM_FILL_IP) ? sccsum::kFlagFillIp : 0u) | sccsum::kFlagFillNow;
+        const uint32_t flags = sccsum::fill_flags(mode) | sccsum::kFlagFillNow;
         // a small one on the row kernel, as small verifies run (launch()), when
         // max_len says its frames fit the exact fast path (128 KiB).  max_len is
         // only a hint: a longer frame there is summed by the row kernel's exact
         // redo, its header read from the frame, just more slowly
         if (sccsum::t_knobs.variant == 0 && n <= sccsum::kSmallRowsMax && max_len != 0 && max_len <= sccsum::kExactMax) {
             return static_cast<int>(sccsum::launch_rows<true, false, true>(
-                max_len, s, dev, static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, nullptr, d_out2,
+                max_len, T.s, T.dev, static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, nullptr, d_out2,
                 d_status, n, flags));
         }
         return sccsum::launch<true>(d_bytes, bytes_len, d_off, d_len, nullptr, d_out2, d_status, n, max_len, stream,
@@ -4344,35 +4298,32 @@ int sccsum_ipv4_fill(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, c
         // under graph capture, freed once pass 2 is done with it)
         void* scratch = nullptr;
         if (!d_out2) {
-            const hipError_t e = hipMallocAsync(&scratch, 4 * n, s);
+            const hipError_t e = hipMallocAsync(&scratch, 4 * n, T.s);
             if (e != hipSuccess) return static_cast<int>(e);
         }
         uint16_t* const vals = d_out2 ? d_out2 : static_cast<uint16_t*>(scratch);
-        const uint32_t flags = ((mode & SCCSUM_FILL_L4) ? sccsum::kFlagFillL4 : 0u) |
-                               ((mode & SCCSUM_FILL_ICMP_ECHO) ? sccsum::kFlagFillIcmp : 0u) |
-                               ((mode & SCCSUM_FILL_IP) ? sccsum::kFlagFillIp : 0u);
         int rc = sccsum::launch<true>(d_bytes, bytes_len, d_off, d_len, nullptr, vals, d_status, n, max_len,
-                                      stream, flags);
+                                      stream, sccsum::fill_flags(mode));
 #ifdef SCCSUM_AB_FILL_GEN_ONLY
         if (false) {  // A/B only: the generate pass alone (the frames are not written)
 #else
         if (rc == SCCSUM_OK) {
 #endif
-            const unsigned grid = static_cast<unsigned>((n + sccsum::kBlock - 1) / sccsum::kBlock);
-            rc = static_cast<int>(sccsum::launch_kernel(sccsum::fill_store_kernel, dim3(grid), s,
-                                                        static_cast<uint8_t*>(d_bytes), bytes_len, d_off, d_len,
+            rc = static_cast<int>(sccsum::launch_kernel(sccsum::fill_store_kernel, dim3(sccsum::blocks_for(n)),
+                                                        dim3(sccsum::kBlock), 0, T.s, static_cast<uint8_t*>(d_bytes),
+                                                        bytes_len, d_off, d_len,
                                                         reinterpret_cast<const uint32_t*>(vals), n, mode));
         }
         if (scratch) {
-            const hipError_t e = hipFreeAsync(scratch, s);
+            const hipError_t e = hipFreeAsync(scratch, T.s);
             if (rc == SCCSUM_OK && e != hipSuccess) rc = static_cast<int>(e);
         }
         return rc;
     }
-    const unsigned grid = static_cast<unsigned>((n + sccsum::kBlock - 1) / sccsum::kBlock);
-    return static_cast<int>(sccsum::launch_kernel(sccsum::fill_header_kernel, dim3(grid), s,
-                                                  static_cast<uint8_t*>(d_bytes), bytes_len, d_off, d_len,
-                                                  reinterpret_cast<uint32_t*>(d_out2), d_status, n, mode));
+    return static_cast<int>(sccsum::launch_kernel(sccsum::fill_header_kernel, dim3(sccsum::blocks_for(n)),
+                                                  dim3(sccsum::kBlock), 0, T.s, static_cast<uint8_t*>(d_bytes),
+                                                  bytes_len, d_off, d_len, reinterpret_cast<uint32_t*>(d_out2),
+                                                  d_status, n, mode));
 }
 
 int sccsum_set_kernel_variant(int variant) {
@@ -4493,12 +4444,11 @@ int sccsum_ab_step_times(void* host, uint64_t bytes) {
 int sccsum_read_probe_blocks(void) { return sccsum::current_cu_count() * sccsum::kBlocksPerCU; }
 
 int sccsum_read_probe(const void* d_src, uint64_t bytes, uint64_t* d_sink, void* stream) {
-    if (!d_src || !d_sink || (bytes & 15u) || (reinterpret_cast<uintptr_t>(d_src) & 15u)) return SCCSUM_EINVAL;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    if (const int rc = sccsum::launch_device(s, &dev); rc != SCCSUM_OK) return rc;
-    const unsigned grid = static_cast<unsigned>(sccsum::cu_count(dev) * sccsum::kBlocksPerCU) & ~7u;
-    return static_cast<int>(sccsum::launch_kernel(sccsum::read_probe_kernel, dim3(grid), s,
+    if (!d_src || !d_sink || (bytes & 15u) || sccsum::misaligned(d_src, 16)) return SCCSUM_EINVAL;
+    const sccsum::LaunchTarget T(stream);
+    if (T.rc != SCCSUM_OK) return T.rc;
+    const unsigned grid = static_cast<unsigned>(sccsum::cu_count(T.dev) * sccsum::kBlocksPerCU) & ~7u;
+    return static_cast<int>(sccsum::launch_kernel(sccsum::read_probe_kernel, dim3(grid), dim3(sccsum::kBlock), 0, T.s,
                                                   static_cast<const sccsum::u32x4*>(d_src), bytes / 16, d_sink));
 }
 

@@ -37,14 +37,18 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
-#include <tuple>
-#include <type_traits>
-#include <utility>
 
+#include "host_launch.h"
 #include "sccsum.h"
 #include "sccsum_diag.h"
+#include "wave_scan.h"
 
 namespace send {
+
+using host_launch::launch_kernel;
+using host_launch::misaligned;
+using wave_scan::lane_id;
+using wave_scan::wave_inclusive_scan;
 
 constexpr int kWave = 64;
 constexpr int kTileBlock = 1024;                // threads of the count / scan / place kernels: one datagram each
@@ -111,17 +115,6 @@ __device__ __forceinline__ uint64_t count_one(const Batch& B, uint64_t i, uint32
     if (bad) return 0;
     const uint32_t frames = frames_of(len, B.proto[i], B.mtu, B.flags);
     return (uint64_t(frames) << 32) | (len + kIpHdr * frames);
-}
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
-
-__device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t o = __shfl_up(static_cast<unsigned long long>(v), d, kWave);
-        if (lane_id() >= static_cast<uint32_t>(d)) v += o;
-    }
-    return v;
 }
 
 // Inclusive scan over the 1024 threads of a block; *total = the block's sum.
@@ -353,20 +346,6 @@ __global__ __launch_bounds__(kEmitBlock) void send_emit_kernel(Batch B, const ui
 
 // ---------------------------------------------------------------- host side
 
-template <typename... P, typename... A>
-hipError_t launch_kernel(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, A&&... a) {
-    static_assert(sizeof...(P) == sizeof...(A), "argument count");
-    std::tuple<std::decay_t<P>...> t(static_cast<std::decay_t<P>>(std::forward<A>(a))...);
-    void* args[sizeof...(P)];
-    std::apply([&](auto&... x) {
-        size_t i = 0;
-        ((args[i++] = static_cast<void*>(&x)), ...);
-    }, t);
-    return hipLaunchKernel(reinterpret_cast<const void*>(k), grid, block, args, 0, s);
-}
-
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 static_assert(sizeof(sccsum_gather_desc) == 16 && offsetof(sccsum_gather_desc, dst_off) == 8 &&
                   offsetof(sccsum_gather_desc, len) == 12,
               "the emit kernel stores a descriptor as two 64-bit words");
@@ -423,34 +402,29 @@ int sccsum_ipv4_send(const sccsum_send_opts* opts, void* d_l4, uint64_t l4_bytes
     }
     // the launches run on the stream's device, which must be the data's: the current one
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e == hipErrorNoDevice ? SCCSUM_ENODEV : static_cast<int>(e);
-    if (st != nullptr) {
-        hipDevice_t sd = -1;
-        e = hipStreamGetDevice(st, &sd);
-        if (e != hipSuccess) return static_cast<int>(e);
-        if (sd != dev) return SCCSUM_EINVAL;
-    }
+    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
+    hipError_t e = host_launch::stream_devices(st, &dev, &sd);
+    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
+    if (sd != dev) return SCCSUM_EINVAL;
 
     const Batch B{d_off, d_len, d_proto, l4_bytes_len, n, opts->mtu, opts->flags};
     const uint64_t ntiles = tiles_of(n);
     uint64_t* const ws = static_cast<uint64_t*>(d_workspace);
     if (ntiles) {
-        e = launch_kernel(send_count_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), st, B, ws);
+        e = launch_kernel(send_count_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), 0, st, B, ws);
         if (e != hipSuccess) return static_cast<int>(e);
     }
-    e = launch_kernel(send_scan_kernel, dim3(1), dim3(kTileBlock), st, B, ws, ntiles, max_frames, max_out_bytes, d_first,
-                      d_dgram_first, d_total);
+    e = launch_kernel(send_scan_kernel, dim3(1), dim3(kTileBlock), 0, st, B, ws, ntiles, max_frames, max_out_bytes,
+                      d_first, d_dgram_first, d_total);
     if (e != hipSuccess) return static_cast<int>(e);
     if (!ntiles) return SCCSUM_OK;
-    e = launch_kernel(send_place_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), st, B, ws, ntiles,
+    e = launch_kernel(send_place_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), 0, st, B, ws, ntiles,
                       static_cast<uint8_t*>(d_l4), d_l4sum, d_dgram_first, d_status);
     if (e != hipSuccess) return static_cast<int>(e);
     if (max_frames == 0) return SCCSUM_OK;
     const uint64_t blocks = std::min<uint64_t>((max_frames + kEmitTile - 1) / kEmitTile, kEmitMaxBlocks);
     const Out O{d_hdr, d_desc, d_first, d_out_off, d_out_len};
-    e = launch_kernel(send_emit_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kEmitBlock), st, B,
+    e = launch_kernel(send_emit_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kEmitBlock), 0, st, B,
                       static_cast<const uint64_t*>(ws), ntiles, static_cast<const uint8_t*>(d_l4), d_dst, d_id,
                       static_cast<const uint32_t*>(d_dgram_first), opts->src_host, O);
     return static_cast<int>(e);

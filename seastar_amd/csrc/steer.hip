@@ -31,15 +31,19 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
-#include <tuple>
-#include <type_traits>
-#include <utility>
 #include <vector>
 
+#include "host_launch.h"
 #include "sccsum.h"
 #include "sccsum_diag.h"
+#include "wave_scan.h"
 
 namespace steer {
+
+using host_launch::launch_kernel;
+using host_launch::misaligned;
+using wave_scan::lane_id;
+using wave_scan::wave_inclusive_scan;
 
 constexpr int kBlock = 256;              // threads per block of the count / scatter kernels
 constexpr int kWave = 64;
@@ -74,8 +78,6 @@ struct Params {
     uint32_t need;
     uint32_t reject;
 };
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
 
 // Tables into LDS: lds[0 .. rows*128) the reta rows, then the redir table.
 __device__ __forceinline__ void load_tables(const Params& P, uint8_t* lds) {
@@ -157,15 +159,6 @@ __global__ __launch_bounds__(kBlock) void steer_count_kernel(const uint32_t* __r
     }
     __syncthreads();
     if (threadIdx.x < buckets) ws[uint64_t(threadIdx.x) * tile_pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, kWave);
-        if (lane_id() >= static_cast<uint32_t>(d)) v += o;
-    }
-    return v;
 }
 
 // One wave scans one bucket's row of per-tile counts in place (exclusive): each
@@ -291,18 +284,6 @@ __global__ __launch_bounds__(kBlock) void steer_scatter_kernel(const uint32_t* _
 }
 
 // ---------------------------------------------------------------- host side
-
-template <typename... P, typename... A>
-hipError_t launch_kernel(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... a) {
-    static_assert(sizeof...(P) == sizeof...(A), "argument count");
-    std::tuple<std::decay_t<P>...> t(static_cast<std::decay_t<P>>(std::forward<A>(a))...);
-    void* args[sizeof...(P)];
-    std::apply([&](auto&... x) {
-        size_t i = 0;
-        ((args[i++] = static_cast<void*>(&x)), ...);
-    }, t);
-    return hipLaunchKernel(reinterpret_cast<const void*>(k), grid, block, args, lds, s);
-}
 
 bool power_of_two(uint32_t v) { return v != 0 && (v & (v - 1)) == 0; }
 
@@ -458,7 +439,7 @@ int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const ui
     if (!s || (mode != SCCSUM_STEER_DISPATCH && mode != SCCSUM_STEER_HASH2CPU)) return SCCSUM_EINVAL;
     if (!d_status && (need != 0 || reject != 0)) return SCCSUM_EINVAL;
     if (n > 0xFFFFFFFFull) return SCCSUM_EINVAL;  // packet indices are 32-bit
-    if (reinterpret_cast<uintptr_t>(d_first) & 3u) return SCCSUM_EINVAL;
+    if (misaligned(d_first, 4)) return SCCSUM_EINVAL;
     Params P{};
     P.hw_queues = s->map.hw_queues;
     P.redir_size = s->map.redir_size;
@@ -483,21 +464,15 @@ int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const ui
     }
     if (n == 0 && !d_first) return SCCSUM_OK;
     if (!d_first) return SCCSUM_EINVAL;
-    if (n > 0 && (!d_hash || (reinterpret_cast<uintptr_t>(d_hash) & 3u) || (reinterpret_cast<uintptr_t>(d_order) & 3u) ||
-                  !d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 15u))) {
+    if (n > 0 && (!d_hash || misaligned(d_hash, 4) || misaligned(d_order, 4) || !d_workspace ||
+                  misaligned(d_workspace, 16))) {
         return SCCSUM_EINVAL;
     }
     // the launches run on the stream's device, where the tables must lie
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    int cur = 0, dev = 0;
+    hipError_t e = host_launch::stream_devices(st, &cur, &dev);
     if (e != hipSuccess) return static_cast<int>(e);
-    if (st != nullptr) {
-        hipDevice_t sd = -1;
-        e = hipStreamGetDevice(st, &sd);
-        if (e != hipSuccess) return static_cast<int>(e);
-        dev = sd;
-    }
     if (dev != s->device) return SCCSUM_EINVAL;
 
     const uint32_t ntiles = static_cast<uint32_t>((n + kSteerTile - 1) / kSteerTile);

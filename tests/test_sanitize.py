@@ -7,7 +7,8 @@ CMakeLists.txt:140-145), applied to the host side of this path:
 2. checksummer::sum(const packet&) over the reference's packet type
    (tests/cpp/packet_ref.cc; needs /root/reference), g++;
 3. argument validation of every C-ABI entry point, the library's own sources
-   (sccsum.hip host side, burst.cc, pipeline.cc, checksummer.cc) built with
+   (seastar_amd.build.SOURCES: the .hip files' host side, burst.cc,
+   pipeline.cc, checksummer.cc) built with
    hipcc and the sanitizers on the host compilation only
    (`-Xarch_host -fsanitize=...`; device code is not instrumented), run
    without a device (tests/cpp/abi_validate.cc);
@@ -18,6 +19,8 @@ import os
 import subprocess
 
 import pytest
+
+from seastar_amd.build import SOURCES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
@@ -62,16 +65,19 @@ def test_packet_ref_sanitized(tmp_path):
     _exec(exe, tmp_path)
 
 
+def _abi_validate(exe, flags, tmp_path):
+    """tests/cpp/abi_validate.cc with the library's sources, `flags` on the host compilation only."""
+    host_san = []
+    for f in flags:  # each host-only flag right after -Xarch_host
+        host_san += ["-Xarch_host", f]
+    _run(["/opt/rocm/bin/hipcc", "-O1", "-g", "--offload-arch=gfx950", "-std=c++17", *host_san,
+          "-I", os.path.join(REPO, "include"), *SOURCES, os.path.join(REPO, "tests", "cpp", "abi_validate.cc"),
+          "-o", exe], tmp_path)
+
+
 def test_abi_validation_sanitized(tmp_path):
     exe = str(tmp_path / "abi_validate_san")
-    host_san = []
-    for f in SAN:  # each host-only flag right after -Xarch_host
-        host_san += ["-Xarch_host", f]
-    csrc = os.path.join(REPO, "seastar_amd", "csrc")
-    _run(["/opt/rocm/bin/hipcc", "-O1", "-g", "--offload-arch=gfx950", "-std=c++17", *host_san,
-          "-I", os.path.join(REPO, "include"), os.path.join(csrc, "sccsum.hip"), os.path.join(csrc, "checksummer.cc"),
-          os.path.join(csrc, "pipeline.cc"), os.path.join(csrc, "burst.cc"),
-          os.path.join(REPO, "tests", "cpp", "abi_validate.cc"), "-o", exe], tmp_path)
+    _abi_validate(exe, SAN, tmp_path)
     _exec(exe, tmp_path)
 
 
@@ -80,14 +86,7 @@ def test_abi_validation_threads_tsan(tmp_path):
     burst / pipeline constructors' failure paths) driven from 8 threads under
     ThreadSanitizer, host code only: no data race may be reported."""
     exe = str(tmp_path / "abi_validate_tsan")
-    host_san = []
-    for f in ("-fsanitize=thread", "-fno-omit-frame-pointer"):
-        host_san += ["-Xarch_host", f]
-    csrc = os.path.join(REPO, "seastar_amd", "csrc")
-    _run(["/opt/rocm/bin/hipcc", "-O1", "-g", "--offload-arch=gfx950", "-std=c++17", *host_san,
-          "-I", os.path.join(REPO, "include"), os.path.join(csrc, "sccsum.hip"), os.path.join(csrc, "checksummer.cc"),
-          os.path.join(csrc, "pipeline.cc"), os.path.join(csrc, "burst.cc"),
-          os.path.join(REPO, "tests", "cpp", "abi_validate.cc"), "-o", exe], tmp_path)
+    _abi_validate(exe, ("-fsanitize=thread", "-fno-omit-frame-pointer"), tmp_path)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
     r = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
