@@ -41,6 +41,11 @@
  *                       (249-281) and, past the MTU (needs_frag, ip.cc:100-111), the cut
  *                       into fragments (283-294), as header + payload fragment lists —
  *                       no payload byte moves; sccsum_ipv4_send_plan = the count for one
+ *   sccsum_ipv4_reasm   the reassembly branch of ipv4::handle_received_packet  src/net/ip.cc:164-220
+ *                       with ipv4::frag::merge / is_complete (412-437) and packet_merger::merge
+ *                       include/seastar/net/packet-util.hh:45-151, for the keys whose outcome does
+ *                       not depend on arrival order, as fragment lists — no payload byte moves;
+ *                       sccsum_ipv4_frag_records = the fragments of a frames batch as records
  *   sccsum_pseudo_seed  ipv4_traits::{tcp,udp}_pseudo_header_checksum
  *                       include/seastar/net/ip.hh:70-75 (host arithmetic, O(1))
  *
@@ -118,7 +123,8 @@ extern "C" {
  * report SCCSUM_EIDLE only when a published step was left undone.
  * 4, additive (round 7): sccsum_ipv4_fill_desc, sccsum_burst_set_fill.
  * 4, additive (round 8): sccsum_steer_* (rx steering).
- * 4, additive (round 9): sccsum_ipv4_send* (tx send). */
+ * 4, additive (round 9): sccsum_ipv4_send* (tx send).
+ * 4, additive (round 10): sccsum_ipv4_frag_records, sccsum_ipv4_reasm* (rx reassembly). */
 #define SCCSUM_ABI_VERSION 4
 
 #define SCCSUM_OK 0
@@ -839,6 +845,142 @@ int sccsum_ipv4_send(const sccsum_send_opts* opts,
                      uint64_t* d_out_off, uint32_t* d_out_len,
                      uint32_t* d_dgram_first, uint8_t* d_status, uint64_t* d_total,
                      void* d_workspace, void* stream);
+
+/* ---- Rx reassembly: IPv4 fragments merged into fragment-list datagrams -----------
+ * What ipv4::handle_received_packet does with an IP fragment (ip.cc:164-220),
+ * ipv4::frag::merge / is_complete (ip.cc:412-437) and packet_merger::merge
+ * (packet-util.hh:45-151), for a whole batch on the device.  As in Tx send, NO
+ * payload byte moves: a reassembled datagram is one sccsum_gather_desc per
+ * fragment, so the outputs are the arguments of sccsum_spans_desc (the L4
+ * verify, tcp.hh:876-883: result 0) and sccsum_gather as they stand, and the
+ * datagram hashes are what sccsum_steer_run(SCCSUM_STEER_HASH2CPU, ...) takes.
+ * frag_timeout and frag_limit_mem stay host policy (the records' tag).
+ *
+ * sccsum_ipv4_frag_records: one sccsum_frag_rec per accepted frame of a frames
+ * batch, a STABLE compaction in arrival order, and their count.
+ *   d_bytes .. n     the batch, as sccsum_ipv4_frames took it
+ *   d_status         what the frames call wrote for it (required)
+ *   need / reject    frame i is accepted when (d_status[i] & need) == need &&
+ *                    (d_status[i] & reject) == 0, as in sccsum_steer_run (8-bit
+ *                    masks).  The documented default: need = SCCSUM_ST_OK |
+ *                    SCCSUM_ST_IPFRAG, reject = SCCSUM_ST_MALFORMED |
+ *                    SCCSUM_ST_RANGE — the fragments ip.cc:121-144 lets
+ *                    through.  Whatever the masks say, a frame outside the
+ *                    buffer, shorter than 20 bytes or than its IP total length,
+ *                    with 4 * ihl past that length or offset + length past
+ *                    65535 is skipped: its header is not trusted.
+ *   host_address     host order; a frame with another destination is skipped
+ *                    (ip.cc:159-162); 0 accepts any
+ *   tag              copied into every record (the host's arrival stamp)
+ *   d_rec            room for n records, 8-byte aligned; d_count: their number
+ *   d_workspace      sccsum_ipv4_reasm_workspace(n) bytes suffice, 16-byte aligned
+ * Records hold absolute addresses: the fragments of one datagram may lie in
+ * different batches' buffers, which must stay where they are while a record
+ * of theirs is pending.
+ *
+ * sccsum_ipv4_reasm: m records in arrival order (the caller puts the records an
+ * earlier call left pending in front of the new batch's).  Key = ipv4_frag_id
+ * {src, dst, id, proto} (ip.hh:243-256).  A key is PLAIN when, over its records
+ * of this call in offset order, every len > 0, consecutive records do not
+ * overlap (end_j <= offset_j+1) and at most one record has MF clear, the last
+ * one.  For a plain key the reference's result does not depend on arrival
+ * order: it completes exactly when the records tile [0, E) and the MF-clear
+ * one is there, at the last of them to arrive.  Every record lands in exactly
+ * one bucket, d_rec_state[i] (one byte per input record):
+ *   SCCSUM_REASM_COMPLETE  its key is plain, starts at 0, every neighbour
+ *                          touches and the MF-clear record is present
+ *   SCCSUM_REASM_PENDING   its key is plain but not complete, or complete past
+ *                          the capacity prefix (below)
+ *   SCCSUM_REASM_HOST      its key is not plain (overlap, duplicate, empty
+ *                          piece, data past the last fragment): the host replays
+ *                          the key's records, in order, through the reference's
+ *                          own merger, whose rules for them depend on arrival
+ *                          order (packet-util.hh:55-86)
+ * Records are grouped by a stable sort on sccsum_reasm_key_mix(key), 32 bits:
+ * two distinct keys with one mix are both sent to the host bucket whole (never
+ * merged with each other); no other plain key ever goes there.
+ *
+ * Per complete datagram d, in the order of the arrival index of its completing
+ * record — the order ip.cc:180-189 delivers them in:
+ *   d_dgram_first[d]   CSR index into d_desc; one closing entry after the last
+ *   d_desc[...]        {frame + hdr_len, d_dgram_off[d] + offset, len} per
+ *                      record, in offset order
+ *   d_dgram_off[d]     64-bit position in a packed layout starting at 0
+ *   d_dgram_len[d]     E, the datagram's bytes
+ *   d_dgram_seed[d]    sccsum_pseudo_seed(src, dst, proto, E) for TCP / UDP, 0
+ *                      for other protocols (as the frames calls treat ICMP)
+ *   d_dgram_head[d]    index of the offset-0 record, whose IP header is the
+ *                      one frag::merge keeps (ip.cc:416-418)
+ *   d_dgram_last[d]    index of the completing record
+ *   d_dgram_hash[d]    with `key` (host memory, key_len >= 4; both or neither):
+ *                      the SCCSUM_RSS_REASSEMBLED hash of ip.cc:186-197 — src,
+ *                      dst, then the first four datagram bytes when E holds
+ *                      the TCP (20) / UDP (8) header
+ * d_pending / d_host: the records of those buckets, copied, in arrival order.
+ * d_total[4] = {datagrams, descriptors, pending, host} as emitted.  Every
+ * array has room for m entries (d_dgram_first: m + 1).
+ *
+ * Capacity, Tx send's prefix rule: datagram d is emitted only while the packed
+ * layout of datagrams 0..d is <= max_out_bytes (itself <= 2^32 - 1, the reach
+ * of dst_off).  The records of the datagrams that do not fit are PENDING, so
+ * the next call completes them; nothing is written past what was emitted.
+ *
+ * Plain dependent launches on `stream` (a key pass, six count / scan / scatter
+ * passes of a stable radix sort, segmented scans and compactions): no
+ * allocation, no memset, no host synchronisation, no atomic deciding a
+ * position — two runs give identical bytes; capturable.  d_workspace:
+ * sccsum_ipv4_reasm_workspace(m) bytes of device scratch, 16-byte aligned.
+ * Alignment: records, d_desc, d_dgram_off and d_total 8 bytes, the 32-bit
+ * arrays 4.  SCCSUM_EINVAL before any device work: a NULL required pointer,
+ * misalignment, m or n > 2^31 - 1, max_out_bytes > 2^32 - 1, mask bits past
+ * 0xFF, a key without d_dgram_hash or the reverse, key_len < 4, a stream of
+ * another device.  m == 0 writes d_total and d_dgram_first[0] and is SCCSUM_OK;
+ * the other arrays and the workspace may then be NULL.  n == 0 writes d_count. */
+typedef struct sccsum_frag_rec {
+    const void* frame;   /* the frame's IPv4 header, where it lies */
+    uint32_t src, dst;   /* host order */
+    uint16_t id;
+    uint8_t  proto;
+    uint8_t  mf;         /* 1 = MF set */
+    uint16_t offset;     /* ip_hdr::offset(), ip.hh:402: uint16_t(frag << 3) */
+    uint16_t hdr_len;    /* 4 * ihl */
+    uint16_t len;        /* ip total length - 4 * ihl: the bytes merge() keeps */
+    uint16_t reserved;   /* 0 */
+    uint32_t tag;
+} sccsum_frag_rec;
+
+#define SCCSUM_REASM_COMPLETE 1
+#define SCCSUM_REASM_PENDING  2
+#define SCCSUM_REASM_HOST     3
+
+typedef struct sccsum_reasm_out {
+    sccsum_gather_desc* d_desc;   /* m */
+    uint32_t* d_dgram_first;      /* m + 1 */
+    uint64_t* d_dgram_off;        /* m */
+    uint32_t* d_dgram_len;        /* m */
+    uint32_t* d_dgram_seed;       /* m */
+    uint32_t* d_dgram_head;       /* m */
+    uint32_t* d_dgram_last;       /* m */
+    uint32_t* d_dgram_hash;       /* m; NULL iff no key */
+    sccsum_frag_rec* d_pending;   /* m */
+    sccsum_frag_rec* d_host;      /* m */
+    uint8_t* d_rec_state;         /* m */
+    uint64_t* d_total;            /* 4 */
+} sccsum_reasm_out;
+
+int sccsum_ipv4_frag_records(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
+                             const uint8_t* d_status, uint32_t need, uint32_t reject, uint64_t n,
+                             uint32_t host_address, uint32_t tag, sccsum_frag_rec* d_rec, uint32_t* d_count,
+                             void* d_workspace, void* stream);
+
+uint64_t sccsum_ipv4_reasm_workspace(uint64_t m);
+
+int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out_bytes,
+                      const uint8_t* key, uint32_t key_len, const sccsum_reasm_out* out,
+                      void* d_workspace, void* stream);
+
+/* The 32-bit mix of a key that sccsum_ipv4_reasm groups by (O(1), host). */
+uint32_t sccsum_reasm_key_mix(uint32_t src_host, uint32_t dst_host, uint16_t id, uint8_t proto);
 
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);

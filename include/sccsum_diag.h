@@ -118,6 +118,13 @@ int sccsum_steer_tile_packets(void);
 int sccsum_send_tile_datagrams(void);
 int sccsum_send_emit_tile_frames(void);
 
+/* Rx reassembly (sccsum_ipv4_reasm, sccsum_ipv4_frag_records): the records of
+ * one tile of the sort's count and scatter kernels, and of one tile of the
+ * scan kernels (constants of the build; the edge-size tests are built around
+ * them). */
+int sccsum_reasm_sort_tile_records(void);
+int sccsum_reasm_scan_tile_records(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@
 //       net.cc:330-344, ip.cc:197                                 indices grouped by shard, in arrival order)
 //   ipv4::send: the header it prepends and the cut past the    tx_sender (headers + header / payload fragment
 //       MTU  ip.cc:100-111, 244-299                               lists for a batch of L4 datagrams; no copy)
+//   ipv4 reassembly: frag::merge, packet_merger::merge          rx_reassembler (fragment records, complete datagrams
+//       ip.cc:164-220, 412-437, packet-util.hh:45-151              as fragment lists in delivery order; no copy)
 //   per packet as qp::poll_tx / DPDK rx hand them over        burst_queue (host packets, async completion)
 //       net.cc:81-105, dpdk.cc:2190-2204
 //   a shard's steady stream of bursts, polled like its queues  resident_engine (one grid, steps streamed in;
@@ -382,6 +384,66 @@ public:
         const uint32_t d = sccsum_steer_dest(&map, mode, src_cpu, hash);
         if (d == UINT32_MAX) check(SCCSUM_EINVAL, "sccsum_steer_dest");
         return d;
+    }
+};
+
+// Rx reassembly (<sccsum.h> sccsum_ipv4_frag_records / sccsum_ipv4_reasm): the
+// reassembly branch of ipv4::handle_received_packet (ip.cc:164-220) with
+// frag::merge / is_complete (ip.cc:412-437) and packet_merger::merge
+// (packet-util.hh:45-151) for a batch's fragments.  No payload byte moves: a
+// complete datagram is a fragment list for spans_desc (its L4 verify) and
+// sccsum_gather, its hash goes to rx_steering::run.  Keys whose outcome depends
+// on arrival order (overlaps, duplicates) come back in the host bucket, for the
+// stack's own merger; frag_timeout / frag_limit_mem stay with the stack (the
+// records' tag).  Stateless: any thread, any stream of the data's device.
+//   rx_reassembler rx(host_address);
+//   engine.ipv4_frames_rss(batch, key, key_len, SCCSUM_RSS_DISPATCH, nullptr, d_status, d_hash, stream);
+//   rx.records(batch, d_status, now, d_rec + carried, d_count, d_ws, stream);   // behind the carried records
+//   rx.run(d_rec, carried + count, max_bytes, key, key_len, out, d_ws, stream);
+//   engine.spans_desc(out.d_desc, out.d_dgram_first, out.d_dgram_off, out.d_dgram_len, datagrams, 65535,
+//                     nullptr, out.d_dgram_seed, d_l4, d_l4_status, stream);      // 0 = L4 verifies
+//   steer.run(SCCSUM_STEER_HASH2CPU, 0, out.d_dgram_hash, ...);                  // out.d_pending: the next carry
+class rx_reassembler {
+    uint32_t _host;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // host_address: ipv4::_host_address (host order); 0 accepts every destination
+    explicit rx_reassembler(uint32_t host_address) : _host(host_address) {}
+
+    uint32_t host_address() const noexcept { return _host; }
+
+    // bytes of 16-byte aligned device scratch records() over n frames / run() over m records needs
+    static uint64_t workspace(uint64_t m) noexcept { return sccsum_ipv4_reasm_workspace(m); }
+
+    // the 32-bit mix of a key that run() groups by
+    static uint32_t key_mix(uint32_t src_host, uint32_t dst_host, uint16_t id, uint8_t proto) noexcept {
+        return sccsum_reasm_key_mix(src_host, dst_host, id, proto);
+    }
+
+    // One record per fragment of the batch that ip.cc:121-162 lets through, in arrival order, given
+    // the d_status the frames call wrote; *d_count = their number.  need / reject as in rx_steering.
+    void records(const device_packet_batch& b, const uint8_t* d_status, uint32_t tag, sccsum_frag_rec* d_rec,
+                 uint32_t* d_count, void* d_workspace, void* stream,
+                 uint32_t need = SCCSUM_ST_OK | SCCSUM_ST_IPFRAG,
+                 uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE) const {
+        check(sccsum_ipv4_frag_records(b.bytes, b.bytes_len, b.off, b.len, d_status, need, reject, b.n, _host, tag,
+                                       d_rec, d_count, d_workspace, stream),
+              "sccsum_ipv4_frag_records");
+    }
+
+    // m records in arrival order, the pending ones of the last run first.  key may be null (then
+    // out.d_dgram_hash must be).  Capacity is a prefix rule: what does not fit stays pending.
+    void run(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out_bytes, const uint8_t* key, size_t key_len,
+             const sccsum_reasm_out& out, void* d_workspace, void* stream) const {
+        check(sccsum_ipv4_reasm(d_rec, m, max_out_bytes, key, static_cast<uint32_t>(key_len), &out, d_workspace,
+                                stream),
+              "sccsum_ipv4_reasm");
     }
 };
 

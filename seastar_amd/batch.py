@@ -724,6 +724,180 @@ def ipv4_send(l4: PacketBatch, dst: torch.Tensor, proto: torch.Tensor, mtu: int,
                       max_frames=max_frames, max_out_bytes=max_out_bytes)
 
 
+# sccsum_frag_rec
+REC_DTYPE = np.dtype([("frame", "<u8"), ("src", "<u4"), ("dst", "<u4"), ("id", "<u2"), ("proto", "u1"), ("mf", "u1"),
+                      ("offset", "<u2"), ("hdr_len", "<u2"), ("len", "<u2"), ("reserved", "<u2"), ("tag", "<u4")])
+REC_BYTES = REC_DTYPE.itemsize  # 32
+FRAG_NEED = native.ST_OK | native.ST_IPFRAG          # the fragments ip.cc:121-144 lets through
+FRAG_REJECT = native.ST_MALFORMED | native.ST_RANGE
+
+
+def frag_records_check(b: PacketBatch, status, need, reject, host_address, tag) -> int:
+    """What frag_records refuses before any launch; returns n."""
+    if not isinstance(b, PacketBatch):
+        raise ValueError("b: need a PacketBatch of IPv4 frames")
+    n = b.n
+    if n > native.REASM_MAX_RECORDS:
+        raise ValueError("b: at most 2^31-1 frames")
+    if not isinstance(status, torch.Tensor) or status.dim() != 1:
+        raise ValueError("status: need the 1-D uint8 tensor the frames call wrote, one entry per frame")
+    _need(status, n, torch.uint8, "status", b.device)
+    for v, what in ((need, "need"), (reject, "reject")):
+        if not 0 <= int(v) <= 0xFF:
+            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+    for v, what in ((host_address, "host_address"), (tag, "tag")):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{what}: need 0..2^32-1")
+    return n
+
+
+def frag_records(b: PacketBatch, status: torch.Tensor, need: int = FRAG_NEED, reject: int = FRAG_REJECT,
+                 host_address: int = 0, tag: int = 0, stream=None) -> torch.Tensor:
+    """sccsum_ipv4_frag_records: the accepted frames of a frames batch as
+    sccsum_frag_rec records (REC_DTYPE), in arrival order: a uint8 tensor of 32
+    bytes per record.  Synchronises to size it.  The records point into b.data,
+    which must stay alive while one of them is pending."""
+    lib = native.load()
+    n = frag_records_check(b, status, need, reject, host_address, tag)
+    dev = b.device
+    rec = _scratch(REC_BYTES * max(n, 1), dev, stream)
+    count = _scratch(1, dev, stream, torch.int32)
+    ws = _scratch(int(lib.sccsum_ipv4_reasm_workspace(n)), dev, stream)
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_ipv4_frag_records(
+        ctypes_ptr(b.data), b.bytes_len, None if empty else ctypes_ptr(b.off), None if empty else ctypes_ptr(b.length),
+        None if empty else ctypes_ptr(status), int(need), int(reject), n, int(host_address), int(tag),
+        ctypes_ptr(rec), ctypes_ptr(count), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_ipv4_frag_records")
+    if stream is not None:
+        stream.synchronize()
+    return rec[: REC_BYTES * (int(count.item()) & 0xFFFFFFFF)]
+
+
+@dataclass
+class ReasmResult:
+    """What sccsum_ipv4_reasm wrote (include/sccsum.h, "Rx reassembly").  Every
+    tensor has room for m entries; totals() says how many are written."""
+    records: torch.Tensor      # uint8 [32 m]: the input
+    desc: torch.Tensor         # uint8 [16 m]: one sccsum_gather_desc per record of an emitted datagram
+    dgram_first: torch.Tensor  # int32 [m + 1]: CSR index into desc, and the closing entry
+    dgram_off: torch.Tensor    # int64 [m]: the datagram's position in the packed layout
+    dgram_len: torch.Tensor    # int32 [m]
+    dgram_seed: torch.Tensor   # int32 [m]: the pseudo-header seed (0: not TCP / UDP)
+    dgram_head: torch.Tensor   # int32 [m]: index of the offset-0 record
+    dgram_last: torch.Tensor   # int32 [m]: index of the completing record
+    dgram_hash: torch.Tensor | None  # int32 [m] when a key was given
+    pending_buf: torch.Tensor  # uint8 [32 m]
+    host_buf: torch.Tensor     # uint8 [32 m]
+    rec_state: torch.Tensor    # uint8 [m]: native.REASM_COMPLETE / _PENDING / _HOST
+    total: torch.Tensor        # int64 [4]
+    m: int
+
+    def totals(self) -> tuple:
+        """(datagrams, descriptors, pending records, host records); synchronises."""
+        t = self.total.cpu().numpy()
+        return int(t[0]), int(t[1]), int(t[2]), int(t[3])
+
+    def lists(self) -> tuple:
+        """(desc, first, off, length, seeds, max_len) of the delivered
+        datagrams, as spans_desc takes them; synchronises."""
+        d, k, _, _ = self.totals()
+        ln = self.dgram_len[:d]
+        return (self.desc[: 16 * k], self.dgram_first[: d + 1], self.dgram_off[:d], ln, self.dgram_seed[:d],
+                (int(ln.max().item()) if d else 0))
+
+    @property
+    def hashes(self) -> torch.Tensor | None:
+        """The delivered datagrams' RSS hashes, as Steer.run takes them; synchronises."""
+        return None if self.dgram_hash is None else self.dgram_hash[: self.totals()[0]]
+
+    @property
+    def pending(self) -> torch.Tensor:
+        """The records to put in front of the next call's; synchronises."""
+        return self.pending_buf[: REC_BYTES * self.totals()[2]]
+
+    @property
+    def host(self) -> torch.Tensor:
+        """The records of the keys the host replays through the reference's merger; synchronises."""
+        return self.host_buf[: REC_BYTES * self.totals()[3]]
+
+    def pack(self, stream=None) -> PacketBatch:
+        """The delivered datagrams packed back to back: sccsum_gather of every
+        piece into a new buffer (the one pass that moves payload bytes);
+        synchronises to size it."""
+        desc, _, off, ln, _, max_len = self.lists()
+        d = int(off.numel())
+        nbytes = int((off[-1] + ln[-1]).item()) if d else 0
+        data = _scratch(_round16(nbytes) or 16, self.records.device, stream)
+        if d:
+            native.check(native.load().sccsum_gather(ctypes_ptr(desc), int(desc.numel()) // 16, ctypes_ptr(data),
+                                                     _stream(stream)), "sccsum_gather")
+        return PacketBatch(data=data, off=off, length=ln, bytes_len=nbytes, max_len=max_len)
+
+
+def reasm_check(records, key, max_out_bytes) -> int:
+    """What reassemble refuses before any launch; returns m."""
+    if (not isinstance(records, torch.Tensor) or records.dtype != torch.uint8 or records.dim() != 1
+            or not records.is_contiguous() or records.numel() % REC_BYTES):
+        raise ValueError("records: need a contiguous 1-D uint8 tensor of 32-byte sccsum_frag_rec records")
+    if not records.is_cuda:
+        raise ValueError("records: need a device tensor")
+    m = int(records.numel()) // REC_BYTES
+    if m > native.REASM_MAX_RECORDS:
+        raise ValueError("records: at most 2^31-1 records")
+    if m and records.data_ptr() % 8:
+        raise ValueError("records: need 8-byte alignment")
+    if key is not None and len(bytes(key)) < 4:
+        raise ValueError("key: need at least 4 bytes")
+    if not 0 <= int(max_out_bytes) <= 0xFFFFFFFF:
+        raise ValueError("max_out_bytes: need 0..2^32-1 (descriptor offsets are 32-bit)")
+    return m
+
+
+def reassemble(records: torch.Tensor, key: bytes | None = None, max_out_bytes: int = 0xFFFFFFFF,
+               stream=None) -> ReasmResult:
+    """sccsum_ipv4_reasm: ipv4::handle_received_packet's reassembly branch
+    (ip.cc:164-220) for a batch of fragment records on the device — complete
+    datagrams as fragment lists in completion order, and the pending and host
+    buckets; no payload byte moves.
+
+        status = torch.empty(b.n, dtype=torch.uint8, device=dev)
+        _, hashes = ipv4_frames_rss(b, key, status=status)
+        recs = frag_records(b, status, host_address=me, tag=now)
+        r = reassemble(torch.cat([carry, recs]), key=key)
+        desc, first, off, length, seeds, max_len = r.lists()
+        l4 = spans_desc(desc, first, off, length, max_len, seeds=seeds)      # 0 = the L4 checksum verifies
+        steer.run(r.hashes)
+        carry = r.pending.clone()
+    """
+    lib = native.load()
+    m = reasm_check(records, key, max_out_bytes)
+    dev = records.device
+    k = max(m, 1)
+    t = dict(desc=_scratch(16 * k, dev, stream), dgram_first=_scratch(m + 1, dev, stream, torch.int32),
+             dgram_off=_scratch(k, dev, stream, torch.int64), dgram_len=_scratch(k, dev, stream, torch.int32),
+             dgram_seed=_scratch(k, dev, stream, torch.int32), dgram_head=_scratch(k, dev, stream, torch.int32),
+             dgram_last=_scratch(k, dev, stream, torch.int32),
+             dgram_hash=None if key is None else _scratch(k, dev, stream, torch.int32),
+             pending_buf=_scratch(REC_BYTES * k, dev, stream), host_buf=_scratch(REC_BYTES * k, dev, stream),
+             rec_state=_scratch(k, dev, stream, torch.uint8), total=_scratch(4, dev, stream, torch.int64))
+    ws = _scratch(int(lib.sccsum_ipv4_reasm_workspace(m)) or 16, dev, stream)
+    out = native.ReasmOut(*[_ptr(t[name]) for name in
+                            ("desc", "dgram_first", "dgram_off", "dgram_len", "dgram_seed", "dgram_head", "dgram_last",
+                             "dgram_hash", "pending_buf", "host_buf", "rec_state", "total")])
+    kb, kl = (None, 0) if key is None else _key(key)
+    code = lib.sccsum_ipv4_reasm(ctypes_ptr(records) if m else None, m, int(max_out_bytes),
+                                 None if kb is None else ctypes.addressof(kb), kl, ctypes.addressof(out),
+                                 ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_ipv4_reasm")
+    return ReasmResult(records=records, desc=t["desc"], dgram_first=t["dgram_first"], dgram_off=t["dgram_off"][:m],
+                       dgram_len=t["dgram_len"][:m], dgram_seed=t["dgram_seed"][:m], dgram_head=t["dgram_head"][:m],
+                       dgram_last=t["dgram_last"][:m],
+                       dgram_hash=None if t["dgram_hash"] is None else t["dgram_hash"][:m],
+                       pending_buf=t["pending_buf"], host_buf=t["host_buf"], rec_state=t["rec_state"][:m],
+                       total=t["total"], m=m)
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

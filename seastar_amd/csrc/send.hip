@@ -47,8 +47,6 @@ namespace send {
 
 using host_launch::launch_kernel;
 using host_launch::misaligned;
-using wave_scan::lane_id;
-using wave_scan::wave_inclusive_scan;
 
 constexpr int kWave = 64;
 constexpr int kTileBlock = 1024;                // threads of the count / scan / place kernels: one datagram each
@@ -120,20 +118,7 @@ __device__ __forceinline__ uint64_t count_one(const Batch& B, uint64_t i, uint32
 // Inclusive scan over the 1024 threads of a block; *total = the block's sum.
 // `part` is LDS for one value per wave; the call may be repeated.
 __device__ __forceinline__ uint64_t block_inclusive_scan(uint64_t v, uint64_t* part, uint64_t* total) {
-    const uint32_t wave = threadIdx.x / kWave;
-    const uint64_t incl = wave_inclusive_scan(v);
-    __syncthreads();  // the last call's readers are done with part
-    if (lane_id() == kWave - 1) part[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kTileWaves; ++w) {
-        const uint64_t p = part[w];
-        if (static_cast<uint32_t>(w) < wave) before += p;
-        all += p;
-    }
-    *total = all;
-    return before + incl;
+    return wave_scan::block_inclusive_scan<kTileWaves>(v, part, total);
 }
 
 __global__ __launch_bounds__(kTileBlock) void send_count_kernel(Batch B, uint64_t* __restrict__ ws) {

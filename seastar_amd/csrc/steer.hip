@@ -33,6 +33,7 @@
 #include <new>
 #include <vector>
 
+#include "bucket_pass.h"
 #include "host_launch.h"
 #include "sccsum.h"
 #include "sccsum_diag.h"
@@ -40,6 +41,9 @@
 
 namespace steer {
 
+using bucket_pass::lanes_below;
+using bucket_pass::match_bucket;  // a packet's peers of the same bucket in its wave
+using bucket_pass::scan_row;      // one bucket's row of per-tile counts, scanned in place
 using host_launch::launch_kernel;
 using host_launch::misaligned;
 using wave_scan::lane_id;
@@ -102,20 +106,6 @@ __device__ __forceinline__ uint32_t bucket_of(const Params& P, const uint8_t* ld
     return lds[q * kRetaSize + ((hash >> P.table_bits) & (kRetaSize - 1))];
 }
 
-// The lanes of the wave whose bucket equals this lane's, among the valid ones:
-// eight ballots, one per bit of the 8-bit bucket.
-__device__ __forceinline__ uint64_t match_bucket(uint32_t b, bool valid) {
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-        const uint64_t set = __ballot((b >> bit) & 1u);
-        m &= ((b >> bit) & 1u) ? set : ~set;
-    }
-    return m;
-}
-
-__device__ __forceinline__ uint64_t lanes_below() { return (uint64_t(1) << lane_id()) - 1u; }
-
 // Loads a tile's hashes and status bytes (all loads issued before any use) and
 // turns them into buckets.
 __device__ __forceinline__ void tile_buckets(const Params& P, const uint8_t* lds, const uint32_t* __restrict__ d_hash,
@@ -159,31 +149,6 @@ __global__ __launch_bounds__(kBlock) void steer_count_kernel(const uint32_t* __r
     }
     __syncthreads();
     if (threadIdx.x < buckets) ws[uint64_t(threadIdx.x) * tile_pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-// One wave scans one bucket's row of per-tile counts in place (exclusive): each
-// lane takes four consecutive tiles (one 16-byte load), the lanes' sums are
-// scanned across the wave, 256 tiles at a time with the sum carried along.
-// Returns the row's total (the same in every lane).
-__device__ __forceinline__ uint32_t scan_row(uint32_t* __restrict__ ws, uint32_t b, uint32_t ntiles,
-                                             uint32_t tile_pitch) {
-    uint4* const row = reinterpret_cast<uint4*>(ws + uint64_t(b) * tile_pitch);
-    const uint32_t lane = lane_id();
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < ntiles; base += kWave * 4) {
-        const uint32_t t = base + lane * 4;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (t < ntiles) v = row[t / 4];
-        if (t + 1 >= ntiles) v.y = 0;  // the row's padding up to tile_pitch
-        if (t + 2 >= ntiles) v.z = 0;
-        if (t + 3 >= ntiles) v.w = 0;
-        const uint32_t sum = v.x + v.y + v.z + v.w;
-        const uint32_t incl = wave_inclusive_scan(sum);
-        const uint32_t ex = carry + incl - sum;
-        if (t < ntiles) row[t / 4] = make_uint4(ex, ex + v.x, ex + v.x + v.y, ex + v.x + v.y + v.z);
-        carry += __shfl(incl, kWave - 1, kWave);
-    }
-    return carry;
 }
 
 // One wave: the bucket totals scanned into d_first (ncpu + 2 entries).

@@ -128,6 +128,13 @@ _PROTOS = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sccsum_send_tile_datagrams": (ctypes.c_int, []),
     "sccsum_send_emit_tile_frames": (ctypes.c_int, []),
+    "sccsum_ipv4_frag_records": (ctypes.c_int, [_vp, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp,
+                                                _vp]),
+    "sccsum_ipv4_reasm_workspace": (_u64, [_u64]),
+    "sccsum_ipv4_reasm": (ctypes.c_int, [_vp, _u64, _u64, _vp, _u32, _vp, _vp, _vp]),
+    "sccsum_reasm_key_mix": (_u32, [_u32, _u32, ctypes.c_uint16, ctypes.c_uint8]),
+    "sccsum_reasm_sort_tile_records": (ctypes.c_int, []),
+    "sccsum_reasm_scan_tile_records": (ctypes.c_int, []),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -181,6 +188,27 @@ SEND_L4_MAX = 65515  # the longest L4 datagram ipv4::send takes (ip_packet_len_m
 class SendOpts(ctypes.Structure):
     """sccsum_send_opts: what ipv4::send takes from its interface (source address, MTU, offload flags)."""
     _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+REASM_COMPLETE = 1
+REASM_PENDING = 2
+REASM_HOST = 3
+REASM_MAX_RECORDS = 0x7FFFFFFF
+
+
+class FragRec(ctypes.Structure):
+    """sccsum_frag_rec: one IPv4 fragment as rx reassembly takes it (32 bytes)."""
+    _fields_ = [("frame", ctypes.c_void_p), ("src", ctypes.c_uint32), ("dst", ctypes.c_uint32),
+                ("id", ctypes.c_uint16), ("proto", ctypes.c_uint8), ("mf", ctypes.c_uint8),
+                ("offset", ctypes.c_uint16), ("hdr_len", ctypes.c_uint16), ("len", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16), ("tag", ctypes.c_uint32)]
+
+
+class ReasmOut(ctypes.Structure):
+    """sccsum_reasm_out: the device arrays sccsum_ipv4_reasm writes."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("d_desc", "d_dgram_first", "d_dgram_off", "d_dgram_len", "d_dgram_seed", "d_dgram_head",
+                 "d_dgram_last", "d_dgram_hash", "d_pending", "d_host", "d_rec_state", "d_total")]
 
 
 class Fragment(ctypes.Structure):
