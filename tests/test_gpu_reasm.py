@@ -13,6 +13,7 @@ import torch
 
 import oracle
 import reasm_model
+from fast_models import key_mix as np_key_mix
 from seastar_amd import batch, native, synth
 from test_gpu_send import SRC, _datagrams, _dev_inputs
 from test_reasm_host import key_mix
@@ -697,18 +698,6 @@ def test_host_bucket_holds_exactly_the_non_plain_keys(dev):
     assert set(got_held) == {k for k in want_held if k in host_keys}
 
 
-def _np_key_mix(src, dst, ident, proto):
-    def fmix(h):
-        h = h ^ (h >> np.uint32(16))
-        h = h * np.uint32(0x85EBCA6B)
-        h = h ^ (h >> np.uint32(13))
-        h = h * np.uint32(0xC2B2AE35)
-        return h ^ (h >> np.uint32(16))
-    h = fmix(src + np.uint32(0x9E3779B9))
-    h = fmix(h ^ dst)
-    return fmix(h + ((ident << np.uint32(8)) | proto) * np.uint32(0x9E3779B1))
-
-
 def test_two_keys_of_one_mix_go_to_the_host_whole(dev):
     """The sort groups by sccsum_reasm_key_mix: two distinct keys that share
     it (found among 2^18 random keys) are both host, whole; their neighbours
@@ -719,8 +708,7 @@ def test_two_keys_of_one_mix_go_to_the_host_whole(dev):
     dst = rng.integers(1, 2**32, n, dtype=np.uint64).astype(np.uint32)
     ident = rng.integers(0, 65536, n).astype(np.uint32)
     proto = np.full(n, 17, np.uint32)
-    with np.errstate(over="ignore"):
-        mix = _np_key_mix(src, dst, ident, proto)
+    mix = np_key_mix(src, dst, ident, proto)
     order = np.argsort(mix, kind="stable")
     same = np.flatnonzero(mix[order][1:] == mix[order][:-1])
     assert same.size, "no colliding pair among the random keys"
@@ -743,3 +731,149 @@ def test_two_keys_of_one_mix_go_to_the_host_whole(dev):
     assert np.array_equal(alone[others], st[others]) and np.all(alone[~others] == COMPLETE)
     h = Raw(dev, recs.size).run(rec_t)
     _check(h, recs, st, emitted, mem)
+
+
+# ---------------------------------------------------------------- the capacity cut outside tile 0
+
+def test_capacity_cut_in_a_later_scan_tile(dev):
+    """The first datagram that does not fit is completed by the record at slot 0
+    of scan tile 1, at that tile's last slot, and inside tile 2: dg_carry scans
+    the cut tile again on top of the tiles before it.  Also the exact byte
+    total up to a tile's last datagram (it fits: the cut is the next tile's
+    first datagram) and that total minus one."""
+    rng = np.random.Generator(np.random.PCG64(45))
+    _, scan = _tiles()
+    m = 3 * scan + 5
+    recs, _, mem = _direct(dev, rng, _small_specs(), m)
+    # a record that is a whole datagram at both edges of tile 1 (swapped there from tile 0 if need be)
+    alone = np.flatnonzero((recs["mf"] == 0) & (recs["offset"] == 0))
+    spare = [int(i) for i in alone if 8 <= i < scan - 8]
+    for slot in (scan, 2 * scan - 1):
+        if slot not in alone:
+            other = spare.pop()
+            recs[[slot, other]] = recs[[other, slot]]
+    rec_t = torch.from_numpy(recs.view(np.uint8).copy()).to(dev)
+    st_all, all_dg = _expect(recs)
+    assert np.any(st_all == PENDING) and len(all_dg) > 2 * scan
+    last = np.array([d.last for d in all_dg])
+    sums = np.cumsum([d.length for d in all_dg])
+    at = {name: int(np.flatnonzero(last == i)[0]) for name, i in (("slot 0 of tile 1", scan),
+                                                                  ("the last slot of tile 1", 2 * scan - 1))}
+    at["inside tile 2"] = int(np.flatnonzero((last > 2 * scan + 10) & (last < 3 * scan - 10))[3])
+    end_of_tile = {t: int(np.flatnonzero(last < (t + 1) * scan)[-1]) for t in (0, 1)}   # a tile's last datagram
+    assert end_of_tile[0] + 1 == at["slot 0 of tile 1"] and end_of_tile[1] == at["the last slot of tile 1"]
+    raw = Raw(dev, recs.size)
+    cases = [(name, int(sums[d]) - 1, d) for name, d in at.items()]
+    cases += [(f"tile {t} fits", int(sums[d]), d + 1) for t, d in end_of_tile.items()]
+    cases += [("tile 0 less one byte", int(sums[end_of_tile[0]]) - 1, end_of_tile[0])]
+    for name, cap, want in cases:
+        st, emitted = _expect(recs, cap=cap)
+        assert len(emitted) == want, name
+        cut_tile = all_dg[want].last // scan       # the tile of the first datagram that does not fit
+        assert cut_tile >= 1 or name == "tile 0 less one byte", name
+        assert np.count_nonzero(st == PENDING) == recs.size - sum(len(d.pieces) for d in emitted)
+        h = raw.run(rec_t, max_out_bytes=cap)
+        _check(h, recs, st, emitted, mem, msg=f"{name}: cap {cap}")
+    assert {all_dg[want].last // scan for _, _, want in cases} == {0, 1, 2}
+    assert {all_dg[want].last % scan for _, _, want in cases} >= {0, scan - 1}
+
+
+# ---------------------------------------------------------------- hdr_len
+
+def _direct_hdr(dev, rng, specs):
+    """Records of complete UDP datagrams as _direct builds them, with a header
+    length per piece: specs = (piece bytes, [hdr_len of piece 0, 1, ...]).
+    frame = the piece's address - hdr_len."""
+    ids = rng.permutation(65536)[: len(specs)]
+    data, at, streams = [], 64, []
+    for k, (piece, hdr_lens) in enumerate(specs):
+        src, dst = int(rng.integers(1, 2**32)), int(rng.integers(1, 2**32))
+        pieces = len(hdr_lens)
+        length = pieces * piece - (int(rng.integers(0, min(piece, 8))) if pieces > 1 else 0)
+        d = _udp_datagram(rng, src, dst, length)
+        recs = [(at + j * piece - hl, src, dst, int(ids[k]), 17, 1 if j + 1 < pieces else 0, j * piece, hl,
+                 min(piece, length - j * piece), 0, k) for j, hl in enumerate(hdr_lens)]
+        streams.append([recs[int(q)] for q in rng.permutation(pieces)])
+        data.append((at, d))
+        at += length + int(rng.integers(0, 4))
+    buf = rng.integers(0, 256, at + 9, dtype=np.uint8)
+    for o, d in data:
+        buf[o: o + d.size] = d
+    t = torch.from_numpy(buf).to(dev)
+    recs = np.array(_interleave(rng, streams), dtype=REC)
+    recs["frame"] += np.uint64(t.data_ptr())
+    return recs, torch.from_numpy(recs.view(np.uint8).copy()).to(dev), Mem().add(t, buf)
+
+
+def test_header_lengths_other_than_20(dev):
+    """The descriptors and the ports lie at frame + hdr_len: header lengths of
+    20, 24 and 60 within one datagram, the head record's 24 and 60."""
+    rng = np.random.Generator(np.random.PCG64(46))
+    specs = [(16, [24, 20, 60]), (8, [60, 24, 20, 20, 60]), (40, [20, 60]), (24, [24]), (32, [60]), (8, [20, 24]),
+             (1480, [60, 24, 20]), (8, [28, 32, 36, 40, 44, 48, 52, 56] * 9)]
+    recs, rec_t, mem = _direct_hdr(dev, rng, specs)
+    st, emitted = _expect(recs)
+    assert len(emitted) == len(specs) and np.all(st == COMPLETE)
+    assert {int(recs[d.head]["hdr_len"]) for d in emitted} >= {20, 24, 60}
+    assert any({int(recs[r]["hdr_len"]) for r, _, _ in d.pieces} == {20, 24, 60} for d in emitted)
+    h = Raw(dev, recs.size).run(rec_t)
+    _check(h, recs, st, emitted, mem)                   # the descriptor sources, and the hashes: ports at frame + hdr_len
+    _wrapper_checks(rec_t, recs, emitted, mem)          # pack() bytes, the L4 verify through spans_desc
+
+
+def test_frames_with_ip_options_end_to_end(dev):
+    """Frames with ihl 6-15 cut by hand into complete datagrams -> ipv4_frames ->
+    frag_records -> reassemble: every emitted record has hdr_len != 20."""
+    rng = np.random.Generator(np.random.PCG64(47))
+    frames, want_bytes = [], {}
+    for k in range(40):
+        src = int(rng.integers(1, 2**32))
+        pieces = int(rng.choice([2, 3, 5, 9]))
+        piece = 8 * int(rng.integers(1, 12))
+        length = pieces * piece - int(rng.integers(0, 8))
+        d = _udp_datagram(rng, src, HOST, length)
+        want_bytes[(src, HOST, 1000 + k, 17)] = d
+        for j in range(pieces):
+            frames.append(_frame(src, HOST, 1000 + k, 17, 1 if j + 1 < pieces else 0, j * piece // 8,
+                                 d[j * piece: (j + 1) * piece], ihl=int(rng.integers(6, 16)), pad=int(rng.integers(0, 5))))
+    frames = [frames[int(i)] for i in rng.permutation(len(frames))]
+    buf, offs, lens = _pack_frames(rng, frames)
+    b = batch.PacketBatch.from_host(buf, offs, lens, device=dev)
+    status = torch.zeros(b.n, dtype=torch.uint8, device=dev)
+    batch.ipv4_frames(b, status=status)
+    rec_t = batch.frag_records(b, status, host_address=HOST, tag=9)
+    recs = rec_t.cpu().numpy().view(REC)
+    assert recs.size == len(frames) and np.all(recs["hdr_len"] > 20) and len(set(recs["hdr_len"].tolist())) == 10
+    assert np.array_equal(recs["frame"], np.uint64(b.data.data_ptr()) + offs)
+    st, emitted = _expect(recs)
+    assert len(emitted) == 40 and np.all(st == COMPLETE)
+    mem = Mem().add(b.data)
+    h = Raw(dev, recs.size).run(rec_t)
+    _check(h, recs, st, emitted, mem)
+    for d in emitted:
+        assert _bytes_of(d, recs, mem).tobytes() == want_bytes[d.key].tobytes()
+    _wrapper_checks(rec_t, recs, emitted, mem)
+
+
+# ---------------------------------------------------------------- key lengths
+
+KEY_52 = KEY + bytes.fromhex("6d5a56da255b0ec24167253d")
+
+
+@pytest.mark.parametrize("key_len", [4, 5, 13, 16, 39, 52])
+def test_hash_keys_of_other_lengths(dev, key_len):
+    """The key's bits past key_len are zero (toeplitz.hh:78-98 with a short
+    key): dgram_hash against the oracle's toeplitz over src | dst | ports."""
+    rng = np.random.Generator(np.random.PCG64(48))
+    key = KEY_52[:key_len]
+    recs, rec_t, mem = _direct(dev, rng, _small_specs())
+    st, emitted = _expect(recs)
+    h = Raw(dev, recs.size).run(rec_t, key=key)
+    _check(h, recs, st, emitted, key=key, msg=f"key of {key_len} bytes")
+    want = []
+    for d in emitted:
+        hr = recs[d.head]
+        ports = mem.read(int(hr["frame"]) + int(hr["hdr_len"]), 4).tobytes() if d.length >= 8 else b""
+        want.append(oracle.toeplitz(key, d.key[0].to_bytes(4, "big") + d.key[1].to_bytes(4, "big") + ports))
+    assert len(emitted) >= 5 and len(set(want)) > 1
+    assert np.array_equal(h["dgram_hash"][: 4 * len(emitted)].view(np.uint32), np.array(want, np.uint32))
