@@ -702,7 +702,9 @@ int sccsum_gather(const sccsum_gather_desc* d_desc, uint64_t n, void* d_dst, voi
  * Results and status as sccsum_spans / sccsum_ipv4_frames (frames: IPv4
  * header + L4, the header may be split across fragments).  d_desc, d_first,
  * d_off, d_len, d_seed, d_out, d_status: device arrays (aligned to their
- * element size, d_desc to 8).  max_len: the longest packet (sizes the loop).
+ * element size, d_desc to 8).  max_len as for sccsum_spans: a hint, the
+ * upper bound of d_len[] if known (0 = unknown); any value is correct, it only
+ * picks how many 16-byte units a lane loads per pass over a fragment.
  * Any d_off and any d_len value is either summed exactly or refused with
  * SCCSUM_ST_RANGE: dst_off is compared with the 64-bit d_off (+ the bytes
  * before the fragment), so a d_off past 2^32 whose low 32 bits equal dst_off

@@ -35,7 +35,9 @@ int sccsum_set_kernel_variant(int variant);
 int sccsum_set_blocks_per_cu(int blocks);
 
 /* Simple kernel (variant 1): force U, the 16-byte units each lane loads per
- * step (1, 2, 4 or 8; 0 = choose from max_len). */
+ * step (1, 2, 4 or 8; 0 = choose from max_len).  The fragment-list kernel
+ * (the *_desc calls) picks its U by the same rule, so a forced value applies
+ * to it too; it has no 8-unit form, and 8 runs as 4 there. */
 int sccsum_set_group_units(int units);
 
 /* Flat kernel: cap a tile (packets a wave plans at once) at 1..64 (default 64). */
