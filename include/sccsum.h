@@ -984,6 +984,204 @@ int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out
 /* The 32-bit mix of a key that sccsum_ipv4_reasm groups by (O(1), host). */
 uint32_t sccsum_reasm_key_mix(uint32_t src_host, uint32_t dst_host, uint16_t id, uint8_t proto);
 
+/* ---- Link layer: rx demux, ARP learn and lookup, tx Ethernet headers ----------------
+ * The per-packet Ethernet steps of the reference around the IPv4 layer, for a
+ * whole batch on the device (paths relative to the reference tree):
+ *   interface::dispatch_packet   src/net/net.cc:324-357   sccsum_eth_rx
+ *   _arp.learn(from, h.src_ip)   src/net/ip.cc:147-149, include/seastar/net/arp.hh:247-248
+ *                                                          sccsum_arp_learn_records
+ *   ipv4::get_l2_dst_address     ip.cc:231-242, arp.hh:214-216   \  sccsum_eth_send
+ *   interface's packet provider  net.cc:266-284                  /
+ * The ARP protocol itself (requests, replies, waiters, timeouts) stays on the
+ * host.  No payload byte moves and no atomic decides a position: two runs give
+ * identical bytes; plain dependent launches on `stream`, capturable.
+ *
+ * A MAC is a uint64_t whose low 48 bits are the six wire bytes as a big-endian
+ * number (the first byte on the wire is the most significant); bits 48-63 are
+ * 0.  IPv4 addresses are in host order.
+ *
+ * ARP table.  An immutable device copy of the stack's ARP table (like
+ * sccsum_steer: a changed table is a new object, the old one destroyed once
+ * its stream is synchronised).  entries[n] are host memory, n <= 2^20 (n == 0
+ * allowed, entries may then be NULL); `pad` is ignored; any ip is a valid key,
+ * 0 and 255.255.255.255 included (the reference seeds its table with broadcast
+ * -> ff:ff:ff:ff:ff:ff, arp.hh:153: the caller adds that entry); when an ip
+ * is given twice the later entry wins, as successive learn calls do.  Open
+ * addressing with linear probing from sccsum_arp_table_slot(ip, bits), 16-byte
+ * slots {ip, valid, mac} with the valid word apart from the key; 2^bits slots,
+ * the smallest power of two >= max(16, 2 n), so every probe sequence meets an
+ * empty slot.  create leaves the caller's current device alone; SCCSUM_EINVAL
+ * for out == NULL, entries == NULL with n != 0, n > 2^20 or a MAC with bits
+ * 48-63 set, before the device is looked at; SCCSUM_ENODEV for a device index
+ * out of range.  sccsum_arp_table_lookup is host arithmetic on the object's
+ * own copy: 1 on a hit (*mac written), 0 on a miss or a NULL argument.
+ * sccsum_arp_table_slot is the home slot of a key in a table of 2^bits slots
+ * (bits <= 31; UINT32_MAX past that), exported so that a test can build
+ * colliding keys; sccsum_arp_table_bits is an object's bits (0 for NULL).
+ *
+ * sccsum_eth_rx: dispatch_packet for n wire frames d_bytes[d_off[i] .. +
+ * d_len[i]).  protos[K] (HOST memory, 1 <= K <= 8, distinct) are the registered
+ * eth_proto values in host order, e.g. {0x0800, 0x0806}.  Frame i is
+ *   class k            d_len >= 14 and the big-endian 16 bits at +12 == protos[k]
+ *   SCCSUM_ETH_UNKNOWN another eth_proto (_proto_map.find fails)
+ *   SCCSUM_ETH_SHORT   d_len < 14 (get_header<eth_hdr> is null)
+ *   SCCSUM_ETH_RANGE   [off, off + len) not inside [0, bytes_len), the 64-bit
+ *                      test of sccsum_spans, made first: the frame is not read
+ * and the last three are dropped.  As in the reference there is no VLAN
+ * handling, no destination-MAC filter and no padding to a minimum length.
+ *   d_class[n]    optional, arrival order: k or one of the three codes
+ *   d_first[K+2]  bucket bases as sccsum_steer_run writes them: bucket k < K is
+ *                 class k, bucket K the dropped frames, the last entry n
+ *   d_order[n]    frame indices grouped by bucket, a STABLE partition (arrival
+ *                 order inside a bucket)
+ *   d_l3_off[n], d_l3_len[n], d_src_mac[n]   in grouped order (position j
+ *                 describes frame d_order[j]): off + 14, len - 14 and the source
+ *                 MAC for a classified frame (trim_front(14)); off, 0 and 0 for
+ *                 a dropped one
+ * so d_l3_off + d_first[k], d_l3_len + d_first[k], d_first[k+1] - d_first[k]
+ * are a frames batch for sccsum_ipv4_frames* as they stand, and an ARP bucket
+ * is the short index list the host copies back.  Three launches (count, scan,
+ * scatter) over tiles of sccsum_eth_tile_packets() frames.  d_workspace:
+ * sccsum_eth_rx_workspace(n) bytes, 16-byte aligned.  n <= 2^32 - 1.  n == 0
+ * writes d_first (all 0) and is SCCSUM_OK; the frame arrays may then be NULL.
+ *
+ * sccsum_arp_learn_records: the learn candidates of ip.cc:147-149 among the n
+ * frames of an IPv4 bucket, given as the frames batch above with the d_status
+ * the frames call wrote for it and the bucket's slice of d_src_mac.  A STABLE
+ * compaction in arrival order of sccsum_arp_rec {ip, index (into the bucket),
+ * mac} into d_rec (room for n, 8-byte aligned) and their number in *d_count.
+ * Frame i is kept when (d_status[i] & need) == need && (d_status[i] & reject)
+ * == 0 (8-bit masks; the documented default need = SCCSUM_ST_OK, reject =
+ * SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE is what ip.cc:121-144 lets through:
+ * fragments pass, and so do packets for other destinations), its source
+ * address src (header bytes 12-15) has ((src ^ host) & netmask) == 0 and src
+ * != host, and `table` does not already map src to this MAC (a NULL table maps
+ * nothing).  Whatever the masks say, a frame outside the buffer or shorter
+ * than 20 bytes is skipped before its header is read.  The host applies the
+ * records in order with the stack's own learn; in the steady state there are
+ * none.  Repeats of one new (ip, mac) pair inside a batch are NOT removed.
+ * d_workspace: sccsum_arp_learn_workspace(n) bytes, 16-byte aligned.  n <=
+ * 2^31 - 1; n == 0 writes *d_count = 0.
+ *
+ * sccsum_eth_send: resolve the next hop of n datagrams and prepend the
+ * Ethernet header to their frames, on fragment lists.  d_dst[n] are the
+ * datagrams' destinations; d_dgram_first[n + 1] as sccsum_ipv4_send wrote it
+ * (datagram i's frames are [d_dgram_first[i], d_dgram_first[i+1])), or NULL:
+ * one frame per datagram (then F == n).  The F frames are fragment lists
+ * d_desc, d_first[F + 1], d_off[F], d_len[F] as the *_desc calls take them,
+ * with any number of descriptors per frame.  Run the checksum fills on those
+ * lists BEFORE this call: an Ethernet descriptor in front of the IP header is
+ * outside sccsum_ipv4_fill_desc's packet.
+ *   Next hop of datagram i: d_dst[i] when ((dst ^ host) & netmask) == 0, gw
+ * otherwise (netmask 0, the reference's initial value, puts every destination
+ * on the link); it is RESOLVED when the table maps it.  A datagram without a
+ * frame (refused by send, or past its prefix) is not looked up: status 0,
+ * never listed.
+ *   Input frame f of a resolved datagram becomes emitted frame f' (a stable
+ * compaction over frames) at layout position o', positions packed back to
+ * back from 0, each frame 14 bytes longer:
+ *   d_eth[14 f' .. + 14)   dst MAC, src MAC = hw_address, eth_proto, big-endian
+ *                          as hton(eth_hdr) leaves them
+ *   d_desc_out             {d_eth + 14 f', o', 14}, then the frame's own
+ *                          descriptors with dst_off - d_off[f] + o' + 14 (32-bit
+ *                          arithmetic) and the same src and len; room for D + F
+ *                          records, D the input's descriptor count (D + F <=
+ *                          2^32 - 1)
+ *   d_first_out[f']        CSR index into d_desc_out, one closing entry after
+ *                          the last emitted frame (room for F + 1)
+ *   d_off_out[f'] = o', d_len_out[f'] = d_len[f] + 14, d_frame_src[f'] = f
+ * so sccsum_gather over d_desc_out yields packed wire frames, and the mapped
+ * burst form takes the lists as they stand.
+ *   d_status[n]       SCCSUM_ST_OK: resolved and emitted; SCCSUM_ST_NOARP:
+ *                     unresolved, no frame emitted; 0: no frame, or past the
+ *                     capacity prefix
+ *   d_unresolved[n]   stable list of {datagram index, next hop} of the
+ *                     SCCSUM_ST_NOARP datagrams: the host sends its ARP queries
+ *                     and resubmits
+ *   d_total[6]        {frames the resolved datagrams need, layout bytes they
+ *                     need, datagrams taken (the prefix), unresolved in the
+ *                     prefix}, then what was emitted: {frames, descriptors}
+ *                     (the sizes of the per-frame arrays and of d_desc_out)
+ * Capacity, Tx send's prefix rule: datagrams are taken in order while the
+ * layout bytes of the resolved ones are <= max_out_bytes (itself <= 2^32 - 1);
+ * from the first resolved datagram that does not fit onward nothing is emitted
+ * or listed and the status is 0.  No array is written past what was emitted;
+ * a rerun with the reported need emits everything.
+ *   Four launches (count, scan, place, emit) over tiles of
+ * sccsum_eth_tile_packets() datagrams.  d_workspace: sccsum_eth_send_workspace(n)
+ * bytes, 16-byte aligned.  n <= 2^32 - 1, F <= 2^31 - 1.  n == 0 writes
+ * d_total and d_first_out[0] and is SCCSUM_OK.
+ *
+ * Alignment: d_off, d_src_mac, records, descriptors, d_off_out, d_unresolved
+ * and d_total 8 bytes; the 32-bit arrays 4; d_bytes and d_eth any.
+ * SCCSUM_EINVAL before any device work, in every call: a NULL required
+ * pointer, misalignment, K outside 1..8 or duplicate protos, a MAC with bits
+ * 48-63 set, mask bits past 0xFF, n / F / max_out_bytes out of range, F != n
+ * without d_dgram_first, a stream of another device than the current one (than
+ * the table's, when a table is given). */
+#define SCCSUM_ST_NOARP    0x20u /* eth_send: the next hop has no ARP entry, no frame emitted */
+#define SCCSUM_ETH_UNKNOWN 0xFFu
+#define SCCSUM_ETH_SHORT   0xFEu
+#define SCCSUM_ETH_RANGE   0xFDu
+#define SCCSUM_ETH_MAX_PROTOS 8
+#define SCCSUM_ARP_MAX_ENTRIES (1u << 20)
+
+typedef struct sccsum_arp_table sccsum_arp_table;
+typedef struct sccsum_arp_entry {
+    uint32_t ip;
+    uint32_t pad;
+    uint64_t mac;
+} sccsum_arp_entry;
+
+typedef struct sccsum_arp_rec {
+    uint32_t ip;
+    uint32_t index;
+    uint64_t mac;
+} sccsum_arp_rec;
+
+typedef struct sccsum_eth_opts {
+    uint64_t hw_address; /* interface::_hw_address */
+    uint32_t host;       /* ipv4::_host_address */
+    uint32_t netmask;    /* ipv4::_netmask */
+    uint32_t gw;         /* ipv4::_gw_address */
+    uint16_t eth_proto;  /* host order, 0x0800 for IPv4 */
+} sccsum_eth_opts;
+
+typedef struct sccsum_eth_unresolved {
+    uint32_t dgram;
+    uint32_t next_hop;
+} sccsum_eth_unresolved;
+
+int sccsum_arp_table_create(int device, const sccsum_arp_entry* entries, uint32_t n, sccsum_arp_table** out);
+/* The same table without a device copy, for sccsum_arp_table_lookup alone (a
+ * control plane that has no device at hand): the device calls refuse it with
+ * SCCSUM_ENODEV, after their argument checks. */
+int sccsum_arp_table_create_host(const sccsum_arp_entry* entries, uint32_t n, sccsum_arp_table** out);
+int sccsum_arp_table_destroy(sccsum_arp_table* t);
+int sccsum_arp_table_lookup(const sccsum_arp_table* t, uint32_t ip, uint64_t* mac);
+uint32_t sccsum_arp_table_slot(uint32_t ip, uint32_t bits);
+uint32_t sccsum_arp_table_bits(const sccsum_arp_table* t);
+
+int sccsum_eth_tile_packets(void);
+uint64_t sccsum_eth_rx_workspace(uint64_t n);
+int sccsum_eth_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len, uint64_t n,
+                  const uint16_t* protos, uint32_t nprotos, uint8_t* d_class, uint32_t* d_first, uint32_t* d_order,
+                  uint64_t* d_l3_off, uint32_t* d_l3_len, uint64_t* d_src_mac, void* d_workspace, void* stream);
+
+uint64_t sccsum_arp_learn_workspace(uint64_t n);
+int sccsum_arp_learn_records(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
+                             const uint8_t* d_status, uint32_t need, uint32_t reject, const uint64_t* d_src_mac,
+                             uint64_t n, uint32_t host, uint32_t netmask, const sccsum_arp_table* table,
+                             sccsum_arp_rec* d_rec, uint32_t* d_count, void* d_workspace, void* stream);
+
+uint64_t sccsum_eth_send_workspace(uint64_t n);
+int sccsum_eth_send(const sccsum_eth_opts* opts, const sccsum_arp_table* table, const uint32_t* d_dst,
+                    const uint32_t* d_dgram_first, uint64_t n, const sccsum_gather_desc* d_desc,
+                    const uint32_t* d_first, const uint64_t* d_off, const uint32_t* d_len, uint64_t nframes,
+                    uint64_t max_out_bytes, uint8_t* d_eth, sccsum_gather_desc* d_desc_out, uint32_t* d_first_out,
+                    uint64_t* d_off_out, uint32_t* d_len_out, uint32_t* d_frame_src, uint8_t* d_status,
+                    sccsum_eth_unresolved* d_unresolved, uint64_t* d_total, void* d_workspace, void* stream);
+
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);
 int sccsum_host_free(void* p);

@@ -24,6 +24,10 @@
 //       MTU  ip.cc:100-111, 244-299                               lists for a batch of L4 datagrams; no copy)
 //   ipv4 reassembly: frag::merge, packet_merger::merge          rx_reassembler (fragment records, complete datagrams
 //       ip.cc:164-220, 412-437, packet-util.hh:45-151              as fragment lists in delivery order; no copy)
+//   interface::dispatch_packet, _arp.learn candidates          eth_rx (frames grouped by eth_proto, trimmed;
+//       net.cc:324-357, ip.cc:147-149                              the learn records of an IPv4 bucket), arp_table
+//   get_l2_dst_address + the interface's eth_hdr               eth_tx (next hop looked up, Ethernet descriptor
+//       ip.cc:231-242, net.cc:266-284                              in front of every frame's list; no copy)
 //   per packet as qp::poll_tx / DPDK rx hand them over        burst_queue (host packets, async completion)
 //       net.cc:81-105, dpdk.cc:2190-2204
 //   a shard's steady stream of bursts, polled like its queues  resident_engine (one grid, steps streamed in;
@@ -38,6 +42,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -514,6 +519,156 @@ public:
                                d_l4sum, l4.n, max_frames, max_out_bytes, out.hdr, out.desc, out.first, out.out_off,
                                out.out_len, out.dgram_first, out.status, out.total, d_workspace, stream),
               "sccsum_ipv4_send");
+    }
+};
+
+// ARP table (<sccsum.h> sccsum_arp_table_*): an immutable device copy of what
+// arp_for<ipv4>::_table holds (arp.hh:153, 214-216, 247-248), for eth_rx::learn
+// and eth_tx::run.  A changed table is a new object; the old one is destroyed
+// once its stream is synchronised.  A MAC is the six wire bytes as a
+// big-endian number in a uint64_t.
+//   sccsum_arp_entry e[] = {{0xFFFFFFFFu, 0, 0xFFFFFFFFFFFFull}, {peer_ip, 0, peer_mac}};
+//   arp_table arp(gpu, e, 2);
+class arp_table {
+    sccsum_arp_table* _t = nullptr;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // entries: host memory, a later entry for the same ip wins; n <= 2^20
+    arp_table(int device, const sccsum_arp_entry* entries, uint32_t n) {
+        check(sccsum_arp_table_create(device, entries, n, &_t), "sccsum_arp_table_create");
+    }
+    // no device copy: lookup() alone
+    arp_table(const sccsum_arp_entry* entries, uint32_t n) {
+        check(sccsum_arp_table_create_host(entries, n, &_t), "sccsum_arp_table_create_host");
+    }
+    arp_table(const arp_table&) = delete;
+    arp_table& operator=(const arp_table&) = delete;
+    ~arp_table() { sccsum_arp_table_destroy(_t); }
+
+    const sccsum_arp_table* get() const noexcept { return _t; }
+    uint32_t bits() const noexcept { return sccsum_arp_table_bits(_t); }
+
+    // host arithmetic: true and *mac on a hit
+    bool lookup(uint32_t ip, uint64_t* mac) const noexcept { return sccsum_arp_table_lookup(_t, ip, mac) != 0; }
+
+    // a key's home slot in a table of 2^bits slots
+    static uint32_t slot(uint32_t ip, uint32_t bits) noexcept { return sccsum_arp_table_slot(ip, bits); }
+};
+
+// Link-layer rx (<sccsum.h> sccsum_eth_rx / sccsum_arp_learn_records):
+// interface::dispatch_packet (net.cc:324-357) for a batch of wire frames — the
+// frames grouped by registered eth_proto with the 14-byte trim, so an IPv4
+// bucket is a frames batch for ipv4_frames* as it stands — and the learn
+// candidates of ip.cc:147-149 among an IPv4 bucket.  Stateless: any thread,
+// any stream of the data's device.
+//   eth_rx rx({0x0800, 0x0806});
+//   rx.run(wire, out, d_ws, stream);                  // out.first copied back: the bucket bounds
+//   device_packet_batch ip{wire.bytes, wire.bytes_len, out.l3_off + first[0], out.l3_len + first[0], count, 0};
+//   engine.ipv4_frames(ip, nullptr, d_status, stream);
+//   rx.learn(ip, d_status, out.src_mac + first[0], host, netmask, &arp, d_rec, d_count, d_ws, stream);
+class eth_rx {
+    uint16_t _protos[SCCSUM_ETH_MAX_PROTOS] = {};
+    uint32_t _k = 0;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays; sizes in <sccsum.h>, "Link layer")
+    struct outputs {
+        uint8_t* cls = nullptr;        // n, optional
+        uint32_t* first = nullptr;     // protos + 2
+        uint32_t* order = nullptr;     // n
+        uint64_t* l3_off = nullptr;    // n
+        uint32_t* l3_len = nullptr;    // n
+        uint64_t* src_mac = nullptr;   // n
+    };
+
+    // the registered eth_proto values (host order), 1..8 distinct ones: bucket k is protos[k]
+    eth_rx(std::initializer_list<uint16_t> protos) {
+        if (protos.size() < 1 || protos.size() > SCCSUM_ETH_MAX_PROTOS) check(SCCSUM_EINVAL, "eth_rx");
+        for (uint16_t p : protos) _protos[_k++] = p;
+    }
+
+    uint32_t protos() const noexcept { return _k; }
+
+    static uint64_t workspace(uint64_t n) noexcept { return sccsum_eth_rx_workspace(n); }
+    static uint64_t learn_workspace(uint64_t n) noexcept { return sccsum_arp_learn_workspace(n); }
+
+    void run(const device_packet_batch& wire, const outputs& out, void* d_workspace, void* stream) const {
+        check(sccsum_eth_rx(wire.bytes, wire.bytes_len, wire.off, wire.len, wire.n, _protos, _k, out.cls, out.first,
+                            out.order, out.l3_off, out.l3_len, out.src_mac, d_workspace, stream),
+              "sccsum_eth_rx");
+    }
+
+    // ip: an IPv4 bucket; d_status what the frames call wrote for it; d_src_mac the bucket's slice.
+    // table may be null (maps nothing).  d_rec has room for ip.n records; *d_count = their number.
+    static void learn(const device_packet_batch& ip, const uint8_t* d_status, const uint64_t* d_src_mac, uint32_t host,
+                      uint32_t netmask, const arp_table* table, sccsum_arp_rec* d_rec, uint32_t* d_count,
+                      void* d_workspace, void* stream, uint32_t need = SCCSUM_ST_OK,
+                      uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE) {
+        check(sccsum_arp_learn_records(ip.bytes, ip.bytes_len, ip.off, ip.len, d_status, need, reject, d_src_mac, ip.n,
+                                       host, netmask, table ? table->get() : nullptr, d_rec, d_count, d_workspace,
+                                       stream),
+              "sccsum_arp_learn_records");
+    }
+};
+
+// Link-layer tx (<sccsum.h> sccsum_eth_send): ipv4::get_l2_dst_address
+// (ip.cc:231-242) per datagram and the Ethernet header the interface's packet
+// provider prepends (net.cc:266-284), on tx_sender's fragment lists after
+// their checksum fills: one more descriptor in front of every frame, no
+// payload byte moves.  Datagrams whose next hop has no ARP entry are listed
+// for the host's ARP queries instead.  Stateless.
+//   eth_tx tx({hw_address, host, netmask, gw, 0x0800});
+//   tx.run(arp, d_dst, send_out.dgram_first, n, send_out.desc, send_out.first, send_out.out_off, send_out.out_len,
+//          frames, max_bytes, out, d_ws, stream);
+class eth_tx {
+    sccsum_eth_opts _opts;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays; sizes in <sccsum.h>, "Link layer")
+    struct outputs {
+        uint8_t* eth = nullptr;                       // 14 * frames bytes
+        sccsum_gather_desc* desc = nullptr;           // descriptors + frames records
+        uint32_t* first = nullptr;                    // frames + 1
+        uint64_t* out_off = nullptr;                  // frames
+        uint32_t* out_len = nullptr;                  // frames
+        uint32_t* frame_src = nullptr;                // frames
+        uint8_t* status = nullptr;                    // n
+        sccsum_eth_unresolved* unresolved = nullptr;  // n
+        uint64_t* total = nullptr;                    // 6
+    };
+
+    explicit eth_tx(const sccsum_eth_opts& opts) : _opts(opts) {}
+
+    const sccsum_eth_opts& opts() const noexcept { return _opts; }
+
+    static uint64_t workspace(uint64_t n) noexcept { return sccsum_eth_send_workspace(n); }
+
+    // d_dgram_first may be null: one frame per datagram (frames == n)
+    void run(const arp_table& table, const uint32_t* d_dst, const uint32_t* d_dgram_first, uint64_t n,
+             const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off, const uint32_t* d_len,
+             uint64_t frames, uint64_t max_out_bytes, const outputs& out, void* d_workspace, void* stream) const {
+        check(sccsum_eth_send(&_opts, table.get(), d_dst, d_dgram_first, n, d_desc, d_first, d_off, d_len, frames,
+                              max_out_bytes, out.eth, out.desc, out.first, out.out_off, out.out_len, out.frame_src,
+                              out.status, out.unresolved, out.total, d_workspace, stream),
+              "sccsum_eth_send");
     }
 };
 

@@ -898,6 +898,396 @@ def reassemble(records: torch.Tensor, key: bytes | None = None, max_out_bytes: i
                        total=t["total"], m=m)
 
 
+# sccsum_arp_rec, sccsum_eth_unresolved
+ARP_REC_DTYPE = np.dtype([("ip", "<u4"), ("index", "<u4"), ("mac", "<u8")])
+ARP_REC_BYTES = ARP_REC_DTYPE.itemsize  # 16
+UNRESOLVED_DTYPE = np.dtype([("dgram", "<u4"), ("next_hop", "<u4")])
+LEARN_NEED = native.ST_OK                               # what ip.cc:121-144 lets through, fragments included
+LEARN_REJECT = native.ST_MALFORMED | native.ST_RANGE
+
+
+def mac_int(mac) -> int:
+    """A MAC as the interface takes it: the six wire bytes as a big-endian
+    number.  Accepts that number, six bytes, or 'aa:bb:cc:dd:ee:ff'."""
+    if isinstance(mac, str):
+        parts = mac.split(":")
+        if len(parts) != 6:
+            raise ValueError(f"mac: need six ':'-separated bytes, got {mac!r}")
+        mac = bytes(int(p, 16) for p in parts)
+    if isinstance(mac, (bytes, bytearray)):
+        if len(mac) != 6:
+            raise ValueError("mac: need six bytes")
+        mac = int.from_bytes(bytes(mac), "big")
+    mac = int(mac)
+    if not 0 <= mac <= native.MAC_MAX:
+        raise ValueError("mac: bits 48-63 must be 0")
+    return mac
+
+
+class ArpTable:
+    """sccsum_arp_table_*: an immutable copy of the stack's ARP table for the
+    device calls below (include/sccsum.h, "Link layer").  `mapping` is a dict
+    {ip: mac} or a sequence of (ip, mac) pairs, where a later pair for the same
+    ip wins; ips in host order, macs as mac_int takes them.  device=None makes
+    a host-only table (lookup alone).  A changed table is a new object."""
+
+    def __init__(self, mapping=(), device: int | None = 0):
+        self._lib = native.load()
+        self._h = None
+        pairs = list(mapping.items()) if hasattr(mapping, "items") else list(mapping)
+        if len(pairs) > native.ARP_MAX_ENTRIES:
+            raise ValueError("mapping: at most 2^20 entries")
+        arr = (native.ArpEntry * max(len(pairs), 1))()
+        for k, (ip, mac) in enumerate(pairs):
+            if not 0 <= int(ip) <= 0xFFFFFFFF:
+                raise ValueError("mapping: an ip is a host-order IPv4 address, 0..2^32-1")
+            arr[k].ip, arr[k].mac = int(ip), mac_int(mac)
+        h = ctypes.c_void_p()
+        entries = ctypes.addressof(arr) if pairs else None
+        if device is None:
+            code = self._lib.sccsum_arp_table_create_host(entries, len(pairs), ctypes.byref(h))
+        else:
+            code = self._lib.sccsum_arp_table_create(int(device), entries, len(pairs), ctypes.byref(h))
+        native.check(code, "sccsum_arp_table_create")
+        self._h = h
+        self.device = None if device is None else torch.device("cuda", int(device))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("ArpTable is closed")
+        return self._h
+
+    @property
+    def bits(self) -> int:
+        return int(self._lib.sccsum_arp_table_bits(self.handle))
+
+    def lookup(self, ip: int):
+        """The MAC the table maps ip to, or None (host arithmetic)."""
+        mac = ctypes.c_uint64()
+        hit = self._lib.sccsum_arp_table_lookup(self.handle, int(ip) & 0xFFFFFFFF, ctypes.byref(mac))
+        return int(mac.value) if hit else None
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            native.check(self._lib.sccsum_arp_table_destroy(h), "sccsum_arp_table_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def _device_table(table, dev, what: str, optional: bool = False):
+    if table is None and optional:
+        return None
+    if not isinstance(table, ArpTable):
+        raise ValueError(f"{what}: need an ArpTable")
+    if table.device != dev:
+        raise ValueError(f"{what}: the table lives on {table.device}, the data on {dev}")
+    return table.handle
+
+
+@dataclass
+class EthRxResult:
+    """What sccsum_eth_rx wrote (include/sccsum.h, "Link layer"): the batch's
+    frames grouped by registered protocol, bucket len(protos) the dropped ones."""
+    frames: PacketBatch       # the wire frames
+    protos: tuple
+    order: torch.Tensor       # int32 [n]: frame indices grouped by bucket, arrival order inside one
+    first: torch.Tensor       # int32 [K + 2]: bucket bases, the last entry n
+    l3_off: torch.Tensor      # int64 [n], grouped order: off + 14 (dropped: off)
+    l3_len: torch.Tensor      # int32 [n], grouped order: len - 14 (dropped: 0)
+    src_mac_all: torch.Tensor  # int64 [n], grouped order (dropped: 0)
+    cls: torch.Tensor | None  # uint8 [n], arrival order: k, or native.ETH_UNKNOWN / ETH_SHORT / ETH_RANGE
+    _bounds: np.ndarray | None = None
+
+    def bounds(self) -> np.ndarray:
+        """first on the host (synchronises once)."""
+        if self._bounds is None:
+            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        return self._bounds
+
+    def _range(self, k: int) -> tuple:
+        if not 0 <= int(k) <= len(self.protos):
+            raise ValueError(f"bucket: need 0..{len(self.protos)}")
+        b = self.bounds()
+        return int(b[k]), int(b[k + 1])
+
+    def bucket(self, k: int) -> PacketBatch:
+        """Bucket k's frames behind their Ethernet header, a frames batch for
+        ipv4_frames* as it stands (no copy)."""
+        a, e = self._range(k)
+        return PacketBatch(data=self.frames.data, off=self.l3_off[a:e], length=self.l3_len[a:e],
+                           bytes_len=self.frames.bytes_len,
+                           max_len=max(self.frames.max_len - native.ETH_HDR, 0) if self.frames.max_len else 0)
+
+    def src_mac(self, k: int) -> torch.Tensor:
+        a, e = self._range(k)
+        return self.src_mac_all[a:e]
+
+    def indices(self, k: int) -> torch.Tensor:
+        """Bucket k's frame indices into the batch, in arrival order."""
+        a, e = self._range(k)
+        return self.order[a:e]
+
+
+def eth_rx_check(b: PacketBatch, protos, cls=None) -> tuple:
+    """What eth_rx refuses before any launch; returns (n, protos as a tuple)."""
+    if not isinstance(b, PacketBatch):
+        raise ValueError("b: need a PacketBatch of wire frames")
+    protos = tuple(int(p) for p in protos)
+    if not 1 <= len(protos) <= native.ETH_MAX_PROTOS:
+        raise ValueError("protos: need 1..8 registered eth_proto values")
+    if len(set(protos)) != len(protos) or any(not 0 <= p <= 0xFFFF for p in protos):
+        raise ValueError("protos: need distinct 16-bit values")
+    if b.n > 0xFFFFFFFF:
+        raise ValueError("b: at most 2^32-1 frames")
+    if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
+        raise ValueError("cls: need a 1-D uint8 tensor of one entry per frame")
+    _need(cls, b.n, torch.uint8, "cls", b.device)
+    return b.n, protos
+
+
+def eth_rx(b: PacketBatch, protos=(0x0800, 0x0806), want_class: bool = True, cls: torch.Tensor | None = None,
+           stream=None) -> EthRxResult:
+    """sccsum_eth_rx: interface::dispatch_packet (net.cc:324-357) for a batch of
+    wire frames — the class of every frame by its eth_proto, a stable partition
+    by class and the 14-byte trim; no byte moves.
+
+        r = eth_rx(wire, (0x0800, 0x0806))
+        ip = r.bucket(0)                              # a frames batch behind the Ethernet headers
+        status = torch.empty(ip.n, dtype=torch.uint8, device=dev)
+        ipv4_frames(ip, status=status)
+        recs = arp_learn_records(ip, status, r.src_mac(0), host, netmask, table)
+        arp_frames = r.indices(1).cpu()               # the short list the host's ARP code takes
+    """
+    lib = native.load()
+    n, protos = eth_rx_check(b, protos, cls)
+    dev = b.device
+    k = len(protos)
+    if cls is None and want_class:
+        cls = _scratch(max(n, 1), dev, stream, torch.uint8)
+    order = _scratch(max(n, 1), dev, stream, torch.int32)
+    first = _scratch(k + 2, dev, stream, torch.int32)
+    l3_off = _scratch(max(n, 1), dev, stream, torch.int64)
+    l3_len = _scratch(max(n, 1), dev, stream, torch.int32)
+    src_mac = _scratch(max(n, 1), dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_eth_rx_workspace(n)), dev, stream)
+    arr = (ctypes.c_uint16 * k)(*protos)
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_eth_rx(ctypes_ptr(b.data), b.bytes_len, None if empty else ctypes_ptr(b.off),
+                             None if empty else ctypes_ptr(b.length), n, ctypes.addressof(arr), k, _ptr(cls),
+                             ctypes_ptr(first), ctypes_ptr(order), ctypes_ptr(l3_off), ctypes_ptr(l3_len),
+                             ctypes_ptr(src_mac), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_eth_rx")
+    return EthRxResult(frames=b, protos=protos, order=order[:n], first=first, l3_off=l3_off[:n], l3_len=l3_len[:n],
+                       src_mac_all=src_mac[:n], cls=None if cls is None else cls[:n])
+
+
+def arp_learn_check(b: PacketBatch, status, src_mac, host, netmask, table, need, reject) -> int:
+    """What arp_learn_records refuses before any launch; returns n."""
+    if not isinstance(b, PacketBatch):
+        raise ValueError("b: need a PacketBatch of IPv4 frames (an eth_rx bucket)")
+    n = b.n
+    if n > 0x7FFFFFFF:
+        raise ValueError("b: at most 2^31-1 frames")
+    for t, dtype, what in ((status, torch.uint8, "status"), (src_mac, torch.int64, "src_mac")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D {dtype} tensor of one entry per frame")
+        _need(t, n, dtype, what, b.device)
+    for v, what in ((need, "need"), (reject, "reject")):
+        if not 0 <= int(v) <= 0xFF:
+            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+    for v, what in ((host, "host"), (netmask, "netmask")):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{what}: need 0..2^32-1")
+    if table is not None:
+        _device_table(table, b.device, "table")
+    return n
+
+
+def arp_learn_records(b: PacketBatch, status: torch.Tensor, src_mac: torch.Tensor, host: int, netmask: int,
+                      table: ArpTable | None = None, need: int = LEARN_NEED, reject: int = LEARN_REJECT,
+                      stream=None) -> torch.Tensor:
+    """sccsum_arp_learn_records: the frames of an IPv4 bucket whose (source
+    ip, source MAC) the stack's _arp.learn (ip.cc:147-149) has to be told, as
+    sccsum_arp_rec records (ARP_REC_DTYPE) in arrival order: a uint8 tensor of
+    16 bytes per record; empty in the steady state.  Repeats of one new pair
+    inside the batch are not removed.  Synchronises to size it."""
+    lib = native.load()
+    n = arp_learn_check(b, status, src_mac, host, netmask, table, need, reject)
+    dev = b.device
+    rec = _scratch(ARP_REC_BYTES * max(n, 1), dev, stream)
+    count = _scratch(1, dev, stream, torch.int32)
+    ws = _scratch(int(lib.sccsum_arp_learn_workspace(n)), dev, stream)
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_arp_learn_records(
+        ctypes_ptr(b.data), b.bytes_len, None if empty else ctypes_ptr(b.off), None if empty else ctypes_ptr(b.length),
+        None if empty else ctypes_ptr(status), int(need), int(reject), None if empty else ctypes_ptr(src_mac), n,
+        int(host), int(netmask), None if table is None else table.handle, ctypes_ptr(rec), ctypes_ptr(count),
+        ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_arp_learn_records")
+    if stream is not None:
+        stream.synchronize()
+    return rec[: ARP_REC_BYTES * (int(count.item()) & 0xFFFFFFFF)]
+
+
+@dataclass
+class EthSendResult:
+    """What sccsum_eth_send wrote (include/sccsum.h, "Link layer").  The
+    per-frame tensors have room for every input frame; totals() and emitted()
+    say how many are written."""
+    eth: torch.Tensor          # uint8 [14 F]: the Ethernet headers
+    desc: torch.Tensor         # uint8 [16 (D + F)]: sccsum_gather_desc records
+    first: torch.Tensor        # int32 [F + 1]: CSR index into desc, and the closing entry
+    out_off: torch.Tensor      # int64 [F]: the frame's position in the packed layout
+    out_len: torch.Tensor      # int32 [F]: the input frame's length + 14
+    frame_src: torch.Tensor    # int32 [F]: the input frame an emitted frame was made of
+    status: torch.Tensor       # uint8 [n]: native.ST_OK, native.ST_NOARP or 0
+    unresolved_buf: torch.Tensor  # uint8 [8 n]: sccsum_eth_unresolved records
+    total: torch.Tensor        # int64 [6]
+    keep: tuple                # the input lists the payload descriptors came from
+
+    def _total(self) -> np.ndarray:
+        return self.total.cpu().numpy()
+
+    def totals(self) -> tuple:
+        """(frames needed, layout bytes needed, datagrams taken, unresolved among them); synchronises."""
+        t = self._total()
+        return int(t[0]), int(t[1]), int(t[2]), int(t[3])
+
+    def emitted(self) -> tuple:
+        """(frames, descriptors) written; synchronises."""
+        t = self._total()
+        return int(t[4]), int(t[5])
+
+    def lists(self) -> tuple:
+        """(desc, first, out_off, out_len, max_len) of the emitted frames, as
+        the *_desc calls and the mapped burst form take them; synchronises."""
+        e, d = self.emitted()
+        ln = self.out_len[:e]
+        return self.desc[: 16 * d], self.first[: e + 1], self.out_off[:e], ln, (int(ln.max().item()) if e else 0)
+
+    def unresolved(self) -> np.ndarray:
+        """The datagrams without an ARP entry as a host array of
+        UNRESOLVED_DTYPE {dgram, next_hop}, in order: the ARP queries to send;
+        synchronises."""
+        u = self.totals()[3]
+        return self.unresolved_buf[: 8 * u].cpu().numpy().view(UNRESOLVED_DTYPE).copy()
+
+    def pack(self, stream=None) -> PacketBatch:
+        """The packed wire frames: sccsum_gather of every header and piece
+        into a new buffer (the one pass that moves payload bytes);
+        synchronises to size it."""
+        desc, _, off, ln, max_len = self.lists()
+        e = int(off.numel())
+        nbytes = int((off[-1] + ln[-1]).item()) if e else 0
+        data = _scratch(_round16(nbytes) or 16, self.eth.device, stream)
+        if e:
+            native.check(native.load().sccsum_gather(ctypes_ptr(desc), int(desc.numel()) // 16, ctypes_ptr(data),
+                                                     _stream(stream)), "sccsum_gather")
+        return PacketBatch(data=data, off=off, length=ln, bytes_len=nbytes, max_len=max_len)
+
+
+def eth_send_check(lists, dst, dgram_first, table, hw_address, host, netmask, gw, eth_proto, max_out_bytes) -> tuple:
+    """What eth_send refuses before any launch (the kernels trust the sizes);
+    returns (n, F, D): datagrams, frames, descriptors."""
+    if not isinstance(lists, (tuple, list)) or len(lists) < 4:
+        raise ValueError("lists: need (desc, first, off, length[, max_len]) as SendResult.lists() returns them")
+    desc, first, off, length = lists[:4]
+    for t, what in ((desc, "desc"), (first, "first"), (off, "off"), (length, "length"), (dst, "dst")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D tensor")
+    dev = off.device
+    nframes = int(off.numel())
+    if nframes > 0x7FFFFFFF:
+        raise ValueError("lists: at most 2^31-1 frames")
+    _need(off, nframes, torch.int64, "off", dev)
+    _need(length, nframes, torch.int32, "length", dev)
+    _need(first, nframes + 1, torch.int32, "first", dev)
+    _need(desc, 0, torch.uint8, "desc", dev)
+    if int(first.numel()) != nframes + 1 or int(length.numel()) != nframes or int(desc.numel()) % 16:
+        raise ValueError("lists: first must have one entry more than off / length, desc 16-byte records")
+    n = int(dst.numel())
+    if n > 0xFFFFFFFF:
+        raise ValueError("dst: at most 2^32-1 datagrams")
+    _need(dst, n, torch.int32, "dst", dev)
+    if dgram_first is None:
+        if n != nframes:
+            raise ValueError("dst: without dgram_first there is one frame per datagram")
+    else:
+        if not isinstance(dgram_first, torch.Tensor) or dgram_first.dim() != 1 or int(dgram_first.numel()) != n + 1:
+            raise ValueError("dgram_first: need a 1-D int32 tensor of n + 1 entries")
+        _need(dgram_first, n + 1, torch.int32, "dgram_first", dev)
+    _device_table(table, dev, "table")
+    mac_int(hw_address)
+    for v, what in ((host, "host"), (netmask, "netmask"), (gw, "gw")):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{what}: need a host-order IPv4 value, 0..2^32-1")
+    if not 0 <= int(eth_proto) <= 0xFFFF:
+        raise ValueError("eth_proto: need a 16-bit value")
+    if max_out_bytes is not None and not 0 <= int(max_out_bytes) <= 0xFFFFFFFF:
+        raise ValueError("max_out_bytes: need 0..2^32-1 (descriptor offsets are 32-bit)")
+    return n, nframes, int(desc.numel()) // 16
+
+
+def eth_send(send, dst: torch.Tensor, table: ArpTable, hw_address, host: int, netmask: int, gw: int,
+             eth_proto: int = 0x0800, dgram_first: torch.Tensor | None = None, max_out_bytes: int | None = None,
+             stream=None) -> EthSendResult:
+    """sccsum_eth_send: ipv4::get_l2_dst_address (ip.cc:231-242) and the
+    interface's Ethernet header (net.cc:266-284) for frames given as fragment
+    lists — a SendResult (after its checksum fills) or a (desc, first, off,
+    length) tuple with dgram_first (None: one frame per datagram).  dst: int32
+    [n], the datagrams' destinations (host-order addresses as uint32 values).
+
+        r = ipv4_send(l4, dst, proto, 1500, me)
+        ipv4_fill_desc(*r.lists()[:4], r.lists()[4], mode=native.FILL_IP)
+        e = eth_send(r, dst, table, hw, me, netmask, gw)
+        wire = e.pack()                 # or hand e.lists() to the mapped burst form
+        for q in e.unresolved(): ...    # arp queries for q["next_hop"], then resubmit datagram q["dgram"]
+    """
+    lib = native.load()
+    if isinstance(send, SendResult):
+        lists = send.lists()
+        dgram_first = send.dgram_first
+    else:
+        lists = send
+    n, nframes, ndesc = eth_send_check(lists, dst, dgram_first, table, hw_address, host, netmask, gw, eth_proto,
+                                       max_out_bytes)
+    desc, first, off, length = lists[:4]
+    dev = off.device
+    if max_out_bytes is None:
+        need = (int(length.to(torch.int64).sum().item()) if nframes else 0) + native.ETH_HDR * nframes
+        max_out_bytes = min(0xFFFFFFFF, need)
+    f1 = max(nframes, 1)
+    eth = _scratch(native.ETH_HDR * f1, dev, stream)
+    desc_out = _scratch(16 * max(ndesc + nframes, 1), dev, stream)
+    first_out = _scratch(nframes + 1, dev, stream, torch.int32)
+    out_off = _scratch(f1, dev, stream, torch.int64)
+    out_len = _scratch(f1, dev, stream, torch.int32)
+    frame_src = _scratch(f1, dev, stream, torch.int32)
+    status = _scratch(max(n, 1), dev, stream, torch.uint8)
+    unresolved = _scratch(8 * max(n, 1), dev, stream)
+    total = _scratch(6, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_eth_send_workspace(n)), dev, stream)
+    opts = native.EthOpts(mac_int(hw_address), int(host), int(netmask), int(gw), int(eth_proto))
+    no_dg, no_fr = n == 0, nframes == 0  # an empty tensor has no address
+    code = lib.sccsum_eth_send(
+        ctypes.addressof(opts), table.handle, None if no_dg else ctypes_ptr(dst), _ptr(dgram_first), n,
+        None if no_fr or not ndesc else ctypes_ptr(desc), None if no_fr else ctypes_ptr(first),
+        None if no_fr else ctypes_ptr(off), None if no_fr else ctypes_ptr(length), nframes, int(max_out_bytes),
+        ctypes_ptr(eth), ctypes_ptr(desc_out), ctypes_ptr(first_out), ctypes_ptr(out_off), ctypes_ptr(out_len),
+        ctypes_ptr(frame_src), ctypes_ptr(status), ctypes_ptr(unresolved), ctypes_ptr(total), ctypes_ptr(ws),
+        _stream(stream))
+    native.check(code, "sccsum_eth_send")
+    return EthSendResult(eth=eth, desc=desc_out, first=first_out, out_off=out_off[:nframes], out_len=out_len[:nframes],
+                         frame_src=frame_src[:nframes], status=status[:n], unresolved_buf=unresolved, total=total,
+                         keep=(send, dst))
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

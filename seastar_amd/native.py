@@ -135,6 +135,21 @@ _PROTOS = {
     "sccsum_reasm_key_mix": (_u32, [_u32, _u32, ctypes.c_uint16, ctypes.c_uint8]),
     "sccsum_reasm_sort_tile_records": (ctypes.c_int, []),
     "sccsum_reasm_scan_tile_records": (ctypes.c_int, []),
+    "sccsum_arp_table_create": (ctypes.c_int, [ctypes.c_int, _vp, _u32, ctypes.POINTER(_vp)]),
+    "sccsum_arp_table_create_host": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(_vp)]),
+    "sccsum_arp_table_destroy": (ctypes.c_int, [_vp]),
+    "sccsum_arp_table_lookup": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(_u64)]),
+    "sccsum_arp_table_slot": (_u32, [_u32, _u32]),
+    "sccsum_arp_table_bits": (_u32, [_vp]),
+    "sccsum_eth_tile_packets": (ctypes.c_int, []),
+    "sccsum_eth_rx_workspace": (_u64, [_u64]),
+    "sccsum_eth_rx": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sccsum_arp_learn_workspace": (_u64, [_u64]),
+    "sccsum_arp_learn_records": (ctypes.c_int, [_vp, _u64, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _u32, _u32, _vp, _vp,
+                                                _vp, _vp, _vp]),
+    "sccsum_eth_send_workspace": (_u64, [_u64]),
+    "sccsum_eth_send": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -209,6 +224,27 @@ class ReasmOut(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in
                 ("d_desc", "d_dgram_first", "d_dgram_off", "d_dgram_len", "d_dgram_seed", "d_dgram_head",
                  "d_dgram_last", "d_dgram_hash", "d_pending", "d_host", "d_rec_state", "d_total")]
+
+
+ST_NOARP = 0x20       # eth_send: the next hop has no ARP entry
+ETH_UNKNOWN = 0xFF    # eth_rx classes of dropped frames
+ETH_SHORT = 0xFE
+ETH_RANGE = 0xFD
+ETH_MAX_PROTOS = 8
+ETH_HDR = 14          # sizeof(eth_hdr)
+ARP_MAX_ENTRIES = 1 << 20
+MAC_MAX = (1 << 48) - 1
+
+
+class ArpEntry(ctypes.Structure):
+    """sccsum_arp_entry: one (ip, mac) pair of an ARP table (16 bytes)."""
+    _fields_ = [("ip", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("mac", ctypes.c_uint64)]
+
+
+class EthOpts(ctypes.Structure):
+    """sccsum_eth_opts: what eth_send takes from the interface and its ipv4 (addresses in host order)."""
+    _fields_ = [("hw_address", ctypes.c_uint64), ("host", ctypes.c_uint32), ("netmask", ctypes.c_uint32),
+                ("gw", ctypes.c_uint32), ("eth_proto", ctypes.c_uint16)]
 
 
 class Fragment(ctypes.Structure):
