@@ -625,6 +625,149 @@ def test_eth_send_scale_and_determinism(dev, send_tables):
     del keep
 
 
+def single_desc_frames(dev, rng, n: int, lo: int = 20, hi: int = 60):
+    """n frames of one descriptor each whose bytes lie anywhere in one 1 MiB
+    device buffer of random bytes (sources may overlap: nothing is written
+    through them), packed back to back in the caller's layout."""
+    pool = rng.integers(0, 256, size=1 << 20, dtype=np.uint8)
+    d_pool = _dev(dev, pool)
+    lens = rng.integers(lo, hi + 1, size=n).astype(np.uint32)
+    start = rng.integers(0, pool.size - hi, size=n)
+    off = (np.cumsum(lens, dtype=np.uint64) - lens).astype(np.uint64)
+    first = np.arange(n + 1, dtype=np.uint32)
+    desc = batch.make_desc(d_pool.data_ptr() + start, off & np.uint64(0xFFFFFFFF), lens)
+    lists = (_dev(dev, desc.view(np.uint8)), _u32_dev(dev, first), _u64_dev(dev, off), _u32_dev(dev, lens))
+    host = dict(desc=desc, first=first, off=off, length=lens)
+    return lists, host, (lambda f: pool[int(start[f]):int(start[f]) + int(lens[f])]), d_pool
+
+
+def test_eth_send_emits_more_frames_than_the_emit_grid_has_slots(dev, send_tables):
+    """eth_send_emit_kernel runs at most kEmitMaxBlocks * kEmitBlock = 16 384 *
+    256 threads and strides over the frames past that: 4 194 304 + one tile + 7
+    frames take the loop's second trip (send.hip's twin:
+    test_send_emits_more_frames_than_the_emit_grid_has_slots).  The build
+    exposes no getter for the two constants; the product is stated here."""
+    grid = 16384 * 256
+    n = grid + _tile() + 7
+    rng = np.random.default_rng(14)
+    lists, host, frame_bytes, keep = single_desc_frames(dev, rng, n)
+    dst = destinations(rng, n, "resolved")
+    table, d_table = send_tables[True]
+    got, outs = run_eth_send(dev, d_table, send_opts(), _u32_dev(dev, dst), None, n, lists, 0xFFFFFFFF)
+    want = ref_eth_send(send_opts(), table, dst, None, host["desc"], host["first"], host["off"], host["length"],
+                        0xFFFFFFFF, outs["eth"].ptr)
+    assert int(want["total"][4]) == n == int(want["total"][2]) and int(want["total"][1]) < 0xFFFFFFFF
+    check_eth_send(got, want, "past the emit grid")
+    packed = gathered(dev, outs, got)
+    sample = np.unique(np.concatenate([np.arange(0, 64), np.arange(grid - 300, grid + 300), np.arange(n - 64, n),
+                                       rng.integers(0, grid, 1500), rng.integers(grid, n, 800)]))
+    eth = want["eth"].reshape(-1, ETH)
+    for f in sample.tolist():
+        at, ln = int(want["out_off"][f]), int(want["out_len"][f])
+        assert packed[at:at + ETH].tobytes() == eth[f].tobytes(), f
+        assert np.array_equal(packed[at + ETH:at + ln], frame_bytes(f)), f
+    del keep
+
+
+def test_device_lookup_in_a_large_table(dev):
+    """table_lookup on the device in a table of 2^17 slots (about 50 000
+    entries), a run of colliding keys that wraps past the last slot included,
+    and in a table created with n = 0, through both eth_send and
+    arp_learn_records; destinations and sources half from the table, half not.
+    netmask 0: every address is on the link, so every one of them is looked up."""
+    rng = np.random.default_rng(17)
+    bits = 17
+    run = colliding_keys(bits, (1 << bits) - 2, 14, start=0x0A000100)
+    collide, absent_run = run[:12], run[12:]                         # the same home slot: held, and not held
+    others = colliding_keys(bits, 0, 2, start=0x0B000000)           # pushed along by the wrapped run
+    plain = np.unique(rng.integers(1, 1 << 32, 50000, dtype=np.uint64)).tolist()
+    held = [ip for ip in dict.fromkeys(collide + others + plain) if ip not in absent_run]
+    table = {int(ip): int(mac_of(ip)) for ip in held}
+    d_table, d_empty = batch.ArpTable(table), batch.ArpTable({})
+    assert d_table.bits == bits and d_empty.bits == 4
+    held_a = np.array(held, dtype=np.uint64)
+    n = 2 * _tile() + 7
+    miss = rng.integers(1, 1 << 32, n, dtype=np.uint64)
+    miss = np.where(np.isin(miss, held_a), np.uint64(0), miss)      # 0 is not held
+    pick = np.where(rng.random(n) < 0.5, held_a[rng.integers(0, held_a.size, n)], miss)
+    pick[:2] = absent_run
+    pick[4:4 + len(collide)] = collide
+    pick[20:22] = others
+    assert 0.3 * n < int(np.isin(pick, held_a).sum()) < 0.7 * n
+    opts = send_opts(netmask=0)
+
+    # eth_send: the destinations
+    lists, host, frame_bytes, keep = hand_built(dev, rng, n)
+    dst = pick.astype(np.uint32)
+    for tab, d_tab in ((table, d_table), ({}, d_empty)):
+        got, outs = run_eth_send(dev, d_tab, opts, _u32_dev(dev, dst), None, n, lists, 0xFFFFFFFF)
+        want = ref_eth_send(opts, tab, dst, None, host["desc"], host["first"], host["off"], host["length"], 0xFFFFFFFF,
+                            outs["eth"].ptr)
+        check_eth_send(got, want, ("large table", len(tab)))
+        assert np.array_equal(gathered(dev, outs, got), wire_bytes(want, frame_bytes))
+        e, u = int(want["total"][4]), int(want["total"][3])
+        assert e + u == n and (e == 0 if not tab else 0.3 * n < e < 0.7 * n)
+        if tab:
+            assert np.all(want["status"][4:4 + len(collide)] == native.ST_OK) and np.all(want["status"][:2] == native.ST_NOARP)
+
+    # arp_learn_records: the sources; a held source comes with the held MAC or, every third, with another
+    data, bytes_len, off, length, _, _ = ip_frames(rng, n)
+    length = np.clip(length, 20, 60).astype(np.uint32)               # every frame inside the buffer, with a header
+    off = np.arange(n, dtype=np.uint64) * np.uint64(SLOT)
+    for k in range(4):
+        data[off.astype(np.int64) + 12 + k] = (pick >> np.uint64(24 - 8 * k)) & np.uint64(0xFF)
+    status = np.full(n, native.ST_OK, dtype=np.uint8)
+    src_mac = mac_of(pick) ^ np.where(np.arange(n) % 3 == 0, np.uint64(0x100), np.uint64(0))
+    d = _learn_inputs(dev, data, bytes_len, off, length, status, src_mac)
+    for tab, d_tab in ((table, d_table), ({}, d_empty)):
+        want = ref_learn(data, bytes_len, off, length, status, NEED, REJECT, src_mac, HOST, 0, tab)
+        got = run_learn(dev, d, n, NEED, REJECT, HOST, 0, d_tab)
+        assert got.tobytes() == want.tobytes(), ("large table", len(tab))
+        if tab:
+            assert 0.5 * n < want.size < 0.8 * n     # the misses, and a third of the hits
+            assert not set(collide[1:]) & set(want["ip"][want["index"] % 3 != 0].tolist())
+        else:
+            assert want.size == n
+    d_table.close()
+    d_empty.close()
+    del keep
+
+
+def test_eth_send_with_an_inconsistent_dgram_first(dev, send_tables):
+    """need_of clamps a datagram's frames [dgram_first[i], dgram_first[i + 1])
+    into the frame arrays: entries beyond nframes, and a decreasing pair, which
+    makes one datagram empty and lets the next take ten frames a second time.
+    The first 32 frames belong to no datagram, so the frames asked for still
+    fit the outputs; the result is the restatement's, which clamps the same
+    way, and run_eth_send's guards see nothing written outside."""
+    rng = np.random.default_rng(19)
+    nframes = 2 * _tile() + 7
+    lists, host, frame_bytes, keep = hand_built(dev, rng, nframes)
+    n = 600
+    cuts = np.sort(rng.choice(np.arange(40, nframes - 40), size=n - 4, replace=False))
+    df = np.concatenate([[32], cuts, [nframes + 5, nframes + 1000, 0xFFFFFFFF, 7]]).astype(np.uint32)
+    assert df.size == n + 1
+    df[200] = df[199] - 10                                   # a decreasing pair
+    assert df[201] > df[199] >= 42
+    dst = destinations(rng, n)
+    dst[195:205] = destinations(rng, 10, "resolved")
+    table, d_table = send_tables[True]
+    args = (dst, df, host["desc"], host["first"], host["off"], host["length"])
+    need = ref_eth_send(send_opts(), table, *args, 0xFFFFFFFF, 0)["total"]
+    assert int(need[0]) <= nframes - 16                      # room in every per-frame output
+    for cap in (0xFFFFFFFF, int(need[1]) // 2):
+        got, outs = run_eth_send(dev, d_table, send_opts(), _u32_dev(dev, dst), _u32_dev(dev, df), n, lists, cap)
+        want = ref_eth_send(send_opts(), table, *args, cap, outs["eth"].ptr)
+        check_eth_send(got, want, ("inconsistent dgram_first", cap))
+        assert np.array_equal(gathered(dev, outs, got), wire_bytes(want, frame_bytes))
+    full = ref_eth_send(send_opts(), table, *args, 0xFFFFFFFF, 0)
+    assert full["status"][199] == 0 and full["status"][200] != 0       # the emptied datagram is not looked up
+    assert np.all(full["status"][n - 3:] == 0)                         # nor are those wholly beyond nframes
+    src = full["frame_src"].astype(np.int64)
+    assert int(src.min()) >= 32 and np.any(np.diff(src) < 0)          # ten frames are emitted twice
+    del keep
+
+
 # ---------------------------------------------------------------- the wrappers, end to end
 
 def test_round_trip_through_the_wrappers(dev):
