@@ -46,6 +46,12 @@
  *                       include/seastar/net/packet-util.hh:45-151, for the keys whose outcome does
  *                       not depend on arrival order, as fragment lists — no payload byte moves;
  *                       sccsum_ipv4_frag_records = the fragments of a frames batch as records
+ *   sccsum_udp_rx       the end of ipv4::handle_received_packet  src/net/ip.cc:159-162, 222-227 and
+ *                       ipv4_udp::received  src/net/udp.cc:45-53, 164-173: the datagrams of an IPv4
+ *                       bucket grouped by channel, both headers trimmed; sccsum_udp_rx_reasm =
+ *                       the same for reassembled datagrams
+ *   sccsum_udp_send     N x ipv4_udp::send  src/net/udp.cc:175-197: the header in the payload's
+ *                       headroom, the checksum pass's spans and seeds
  *   sccsum_pseudo_seed  ipv4_traits::{tcp,udp}_pseudo_header_checksum
  *                       include/seastar/net/ip.hh:70-75 (host arithmetic, O(1))
  *
@@ -1181,6 +1187,182 @@ int sccsum_eth_send(const sccsum_eth_opts* opts, const sccsum_arp_table* table, 
                     uint64_t max_out_bytes, uint8_t* d_eth, sccsum_gather_desc* d_desc_out, uint32_t* d_first_out,
                     uint64_t* d_off_out, uint32_t* d_len_out, uint32_t* d_frame_src, uint8_t* d_status,
                     sccsum_eth_unresolved* d_unresolved, uint64_t* d_total, void* d_workspace, void* stream);
+
+/* ---- UDP layer: rx channel demux by port, tx headers in headroom ---------------------
+ * The per-datagram UDP steps of the reference above the IPv4 layer, for a whole
+ * batch on the device (paths relative to the reference tree):
+ *   ipv4::handle_received_packet, its end   src/net/ip.cc:159-162, 222-227  \  sccsum_udp_rx,
+ *   native_datagram, ipv4_udp::received     src/net/udp.cc:45-53, 164-173   /  sccsum_udp_rx_reasm
+ *   ipv4_udp::send                          udp.cc:175-197                     sccsum_udp_send
+ * No payload byte moves and no atomic decides a position: two runs give
+ * identical bytes; plain dependent launches on `stream`, no allocation, no
+ * memset, no host synchronisation; capturable.  Addresses and ports are in host
+ * order.
+ *
+ * Port table.  An immutable device object (like sccsum_arp_table: a changed set
+ * of channels is a new object, the old one destroyed once its stream is
+ * synchronised).  ports[C] are HOST memory, distinct host-order ports, 0 <= C <=
+ * SCCSUM_UDP_MAX_CHANNELS (252; ports may be NULL when C == 0); channel k is
+ * ports[k], what ipv4_udp::_channels maps.  The device form is a 65 536-entry
+ * byte table (port -> k, 0xFF unbound): one byte load per datagram.  create
+ * leaves the caller's current device alone; SCCSUM_EINVAL for out == NULL,
+ * ports == NULL with C != 0, C > 252 or a port given twice, before the device
+ * is looked at; SCCSUM_ENODEV for a device index out of range.
+ * sccsum_udp_ports_lookup is host arithmetic on the object's own copy: k, or -1
+ * for an unbound port or a NULL table; sccsum_udp_ports_channels is C (0 for
+ * NULL).  _create_host makes the same object without a device copy, for lookup
+ * alone: the device calls refuse it with SCCSUM_ENODEV after their argument
+ * checks.
+ *
+ * sccsum_udp_rx: the non-fragment frames of an IPv4 bucket.  The frames batch
+ * (d_bytes, bytes_len, d_off, d_len, nbatch frames) as sccsum_ipv4_frames took
+ * it, the d_status[nbatch] that call wrote, and 8-bit masks: a frame passes when
+ * (d_status & need) == need && (d_status & reject) == 0.  The documented
+ * default is need = SCCSUM_ST_OK, reject = SCCSUM_ST_MALFORMED |
+ * SCCSUM_ST_RANGE | SCCSUM_ST_IPFRAG.  The reference does NOT verify the UDP
+ * checksum on rx (udp.cc:164-173); a caller who wants it verified adds
+ * SCCSUM_ST_L4_OK to need.  host_address: ipv4::_host_address, 0 accepts any
+ * destination.  The call has n frames: frame j is batch frame d_index[j], or
+ * batch frame j when d_index is NULL (then n <= nbatch) — a shard's slice of
+ * sccsum_steer_run's grouped d_order goes in as it stands.
+ *   Class of frame j (d_class[n], optional, in the call's order):
+ *   SCCSUM_UDP_SKIP    not the UDP layer's.  Any of: d_index[j] >= nbatch; it
+ *                      fails the masks; [off, off + len) is not inside [0,
+ *                      bytes_len) (the 64-bit test of sccsum_spans, made before
+ *                      the frame is read); it is shorter than 20 bytes or than
+ *                      its IP total length, or 4 * ihl is past that length (the
+ *                      header-trust rules of sccsum_ipv4_frag_records); MF is
+ *                      set or the fragment offset is nonzero, read from the
+ *                      header; dst != host_address; protocol != 17
+ *   SCCSUM_UDP_SHORT   the L4 length ip_len - 4 * ihl < 8: get_header<udp_hdr>
+ *                      is null there and the reference dereferences it; here
+ *                      the frame is dropped
+ *   SCCSUM_UDP_NOPORT  no channel on the big-endian 16 bits at L4 +2
+ *                      (udp.cc:168-169: dropped silently, as in the reference)
+ *   k                  the channel
+ *   d_first[C + 2]  bucket bases as sccsum_eth_rx writes them: bucket k < C is
+ *                   channel k, bucket C everything dropped, the last entry n
+ *   d_order[n]      batch frame indices (d_index[j], or j) grouped by bucket, a
+ *                   STABLE partition (the call's order inside a bucket)
+ *   d_pay_off[n], d_pay_len[n], d_src[n], d_sport[n]   in grouped order: off + 4
+ *                   ihl + 8, ip_len - 4 ihl - 8, the source address and the
+ *                   source port of a frame with a channel; off, 0, 0, 0 for a
+ *                   dropped one (0 for its off too when its index is out of
+ *                   range).  The length is the trim to the IP total length
+ *                   (ip.cc:225) and then everything behind the two headers:
+ *                   udp_hdr::len is NOT consulted, as native_datagram does not
+ *                   consult it
+ * so d_pay_off + d_first[k], d_pay_len + d_first[k], d_first[k+1] - d_first[k]
+ * are a spans batch as they stand.
+ *   Queue room.  _queue.push drops a datagram when the channel's queue is full
+ * (queue.hh:184-192; ipv4_udp::default_queue_size 1 024).  The partition is
+ * stable, so the datagrams the reference accepts are the first min(count_k,
+ * room_k) of bucket k: host arithmetic on C numbers, which the wrappers offer as
+ * taken(k, room).  The device does not see room.
+ *
+ * sccsum_udp_rx_reasm: the same demux for the m datagrams sccsum_ipv4_reasm
+ * emitted: its d_desc, d_dgram_first[m + 1], d_dgram_off, d_dgram_len,
+ * d_dgram_head and the records d_rec[nrec] it took.  Source, destination and
+ * protocol of datagram d come from d_rec[d_dgram_head[d]]; optional
+ * d_l4_status[m] — what sccsum_spans_desc wrote for the L4 verify — with the
+ * masks as above (NULL: the masks must be 0).  The eight header bytes are read
+ * through the list, at layout positions d_dgram_off[d] + 0..7, byte-wise: the
+ * list is in layout order and tiles the datagram, as reassembly writes it, so
+ * the header may straddle up to eight descriptors; at most eight are walked and
+ * none is read past d_dgram_first[d + 1].  Classes: SKIP (the masks, a head
+ * index >= nrec, destination, protocol, a list whose first eight descriptors do
+ * not hold the eight bytes), SHORT (E = d_dgram_len[d] < 8), NOPORT, k.
+ * Outputs: d_class[m], d_first[C + 2], d_order[m] (datagram indices) and, in
+ * grouped order, d_pay_len = E - 8, d_src, d_sport (0 for a dropped one).  The
+ * payload is the datagram's layout bytes from +8, so sccsum_gather over
+ * reassembly's own descriptors materialises it; no descriptor is rewritten.
+ *
+ * Both are three launches (count, scan, scatter; four past 31 channels) over
+ * tiles of sccsum_eth_tile_packets() items, the two decodes sharing the
+ * kernels: the count kernel decodes every item once and leaves 16 bytes of it
+ * in the workspace for the scatter kernel, which reads no header.  d_workspace:
+ * sccsum_udp_rx_workspace(n) / sccsum_udp_rx_reasm_workspace(m) bytes (16 per
+ * item and the per-tile counts of 253 buckets), 16-byte aligned.  n, nbatch <= 2^32 - 1; m, nrec <= 2^31 - 1.  n == 0
+ * (m == 0) writes d_first (all 0) and is SCCSUM_OK; the other arrays may then
+ * be NULL.
+ *
+ * sccsum_udp_send: ipv4_udp::send's header for n payloads, written where
+ * prepend_header puts it when the packet has headroom: payload i is
+ * d_bytes[d_off[i] .. + d_len[i]) and the 8 bytes in front of it belong to the
+ * call.  The caller's contract: no headroom overlaps another payload or
+ * headroom.  This is the form that composes with sccsum_ipv4_send, which needs
+ * header and payload contiguous.  d_dst[n], d_dport[n], d_sport[n]; opts: the
+ * source address, the MTU (68..65535) and SCCSUM_UDP_* flags.  Per accepted
+ * datagram the call writes at d_off - 8: sport, dport, len + 8 (big-endian),
+ * checksum field 0, and
+ *   d_l4_off = d_off - 8, d_l4_len = d_len + 8     sccsum_ipv4_send's d_off / d_len
+ *   d_proto = 17 (optional array)                  its d_proto
+ *   d_sum_len, d_seed                              with d_l4_off a spans batch whose
+ *                                                  sccsum_spans results are the d_l4sum
+ *                                                  sccsum_ipv4_send(SCCSUM_SEND_L4)
+ *                                                  stores at UDP +6
+ *   d_needs_csum (u8)                              offload_info::needs_csum
+ * Full checksum (udp.cc:191-194): d_sum_len = d_l4_len, d_seed =
+ * sccsum_pseudo_seed(src, dst, 17, d_l4_len); a result of 0 stays 0.  With
+ * SCCSUM_UDP_CSUM_OFFLOAD (tx_csum_l4_offload) and no fragmentation needed
+ * (udp.cc:188-190; needs_frag = d_l4_len + 20 > mtu && !SCCSUM_UDP_UFO,
+ * ip.cc:100-111) the field must hold the folded pseudo-header sum, not
+ * complemented: d_sum_len = 0 and d_seed = 0xFFFF ^ sccsum_pseudo_seed(...), so
+ * the empty span's result is exactly that value, and d_needs_csum = 1.
+ *   d_status[n] (required): SCCSUM_ST_OK; SCCSUM_ST_RANGE: d_off < 8 or [d_off
+ * - 8, d_off + d_len) is not inside [0, bytes_len) (64-bit test);
+ * SCCSUM_ST_MALFORMED: d_len > 65507, sccsum_ipv4_send's 65 515 less the
+ * header; both bits when both hold.  A refused datagram writes nothing into
+ * d_bytes and gets d_l4_off = UINT64_MAX, d_l4_len = d_sum_len = d_seed = 0,
+ * d_needs_csum = 0, so sccsum_ipv4_send refuses it with SCCSUM_ST_RANGE and
+ * emits no frame.  One elementwise kernel; n <= 2^32 - 1; n == 0 is SCCSUM_OK.
+ *
+ * Alignment: d_off, d_pay_off, d_dgram_off, d_l4_off, records and descriptors 8
+ * bytes; the 32-bit arrays 4; the 16-bit arrays 2; d_bytes any.  SCCSUM_EINVAL
+ * before any device work, in every call: a NULL required pointer,
+ * misalignment, a NULL table, mask bits past 0xFF, masks without a status
+ * array, n / nbatch / m / nrec out of range, n > nbatch without d_index, mtu
+ * outside 68..65535, unknown flags, a stream of another device than the
+ * table's (udp_send: than the current one). */
+#define SCCSUM_UDP_NOPORT 0xFFu
+#define SCCSUM_UDP_SHORT  0xFEu
+#define SCCSUM_UDP_SKIP   0xFDu
+#define SCCSUM_UDP_MAX_CHANNELS 252
+#define SCCSUM_UDP_CSUM_OFFLOAD 0x01u /* hw_features().tx_csum_l4_offload (udp.cc:188) */
+#define SCCSUM_UDP_UFO          0x02u /* hw_features().tx_ufo: a UDP datagram is never cut (ip.cc:106) */
+
+typedef struct sccsum_udp_ports sccsum_udp_ports;
+typedef struct sccsum_udp_opts {
+    uint32_t src_host; /* ipv4::_host_address, host order */
+    uint32_t mtu;      /* hw_features().mtu, 68..65535 */
+    uint32_t flags;
+} sccsum_udp_opts;
+
+int sccsum_udp_ports_create(int device, const uint16_t* ports, uint32_t channels, sccsum_udp_ports** out);
+int sccsum_udp_ports_create_host(const uint16_t* ports, uint32_t channels, sccsum_udp_ports** out);
+int sccsum_udp_ports_destroy(sccsum_udp_ports* t);
+int sccsum_udp_ports_lookup(const sccsum_udp_ports* t, uint16_t port);
+uint32_t sccsum_udp_ports_channels(const sccsum_udp_ports* t);
+
+uint64_t sccsum_udp_rx_workspace(uint64_t n);
+int sccsum_udp_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
+                  uint64_t nbatch, const uint8_t* d_status, uint32_t need, uint32_t reject, uint32_t host_address,
+                  const sccsum_udp_ports* ports, const uint32_t* d_index, uint64_t n, uint8_t* d_class,
+                  uint32_t* d_first, uint32_t* d_order, uint64_t* d_pay_off, uint32_t* d_pay_len, uint32_t* d_src,
+                  uint16_t* d_sport, void* d_workspace, void* stream);
+
+uint64_t sccsum_udp_rx_reasm_workspace(uint64_t m);
+int sccsum_udp_rx_reasm(const sccsum_gather_desc* d_desc, const uint32_t* d_dgram_first, const uint64_t* d_dgram_off,
+                        const uint32_t* d_dgram_len, const uint32_t* d_dgram_head, uint64_t m,
+                        const sccsum_frag_rec* d_rec, uint64_t nrec, const uint8_t* d_l4_status, uint32_t need,
+                        uint32_t reject, uint32_t host_address, const sccsum_udp_ports* ports, uint8_t* d_class,
+                        uint32_t* d_first, uint32_t* d_order, uint32_t* d_pay_len, uint32_t* d_src, uint16_t* d_sport,
+                        void* d_workspace, void* stream);
+
+int sccsum_udp_send(const sccsum_udp_opts* opts, void* d_bytes, uint64_t bytes_len, const uint64_t* d_off,
+                    const uint32_t* d_len, const uint32_t* d_dst, const uint16_t* d_dport, const uint16_t* d_sport,
+                    uint64_t n, uint64_t* d_l4_off, uint32_t* d_l4_len, uint32_t* d_sum_len, uint32_t* d_seed,
+                    uint8_t* d_proto, uint8_t* d_needs_csum, uint8_t* d_status, void* stream);
 
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);

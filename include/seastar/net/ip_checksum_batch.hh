@@ -28,6 +28,10 @@
 //       net.cc:324-357, ip.cc:147-149                              the learn records of an IPv4 bucket), arp_table
 //   get_l2_dst_address + the interface's eth_hdr               eth_tx (next hop looked up, Ethernet descriptor
 //       ip.cc:231-242, net.cc:266-284                              in front of every frame's list; no copy)
+//   handle_received_packet's end + ipv4_udp::received          udp_rx (frames / reassembled datagrams grouped by
+//       ip.cc:159-162, 222-227, udp.cc:45-53, 164-173              channel, headers trimmed), udp_ports
+//   ipv4_udp::send  udp.cc:175-197                             udp_tx (the header in the payload's headroom, the
+//                                                                  checksum pass's spans and seeds)
 //   per packet as qp::poll_tx / DPDK rx hand them over        burst_queue (host packets, async completion)
 //       net.cc:81-105, dpdk.cc:2190-2204
 //   a shard's steady stream of bursts, polled like its queues  resident_engine (one grid, steps streamed in;
@@ -669,6 +673,159 @@ public:
                               max_out_bytes, out.eth, out.desc, out.first, out.out_off, out.out_len, out.frame_src,
                               out.status, out.unresolved, out.total, d_workspace, stream),
               "sccsum_eth_send");
+    }
+};
+
+// UDP port table (<sccsum.h> sccsum_udp_ports_*): an immutable device copy of
+// what ipv4_udp::_channels maps (udp.cc:168-169, 235-236): channel k is
+// ports[k].  A changed set of channels is a new object; the old one is
+// destroyed once its stream is synchronised.
+//   const uint16_t bound[] = {53, 10000};
+//   udp_ports ports(gpu, bound, 2);
+class udp_ports {
+    sccsum_udp_ports* _t = nullptr;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // ports: host memory, distinct, host order; channels <= SCCSUM_UDP_MAX_CHANNELS
+    udp_ports(int device, const uint16_t* ports, uint32_t channels) {
+        check(sccsum_udp_ports_create(device, ports, channels, &_t), "sccsum_udp_ports_create");
+    }
+    // no device copy: lookup() alone
+    udp_ports(const uint16_t* ports, uint32_t channels) {
+        check(sccsum_udp_ports_create_host(ports, channels, &_t), "sccsum_udp_ports_create_host");
+    }
+    udp_ports(const udp_ports&) = delete;
+    udp_ports& operator=(const udp_ports&) = delete;
+    ~udp_ports() { sccsum_udp_ports_destroy(_t); }
+
+    const sccsum_udp_ports* get() const noexcept { return _t; }
+    uint32_t channels() const noexcept { return sccsum_udp_ports_channels(_t); }
+
+    // host arithmetic: the channel bound to port, or -1
+    int lookup(uint16_t port) const noexcept { return sccsum_udp_ports_lookup(_t, port); }
+};
+
+// UDP rx (<sccsum.h> sccsum_udp_rx / sccsum_udp_rx_reasm): the end of
+// ipv4::handle_received_packet (ip.cc:159-162, 222-227) and ipv4_udp::received
+// (udp.cc:45-53, 164-173) for a batch — the non-fragment frames of an IPv4
+// bucket, or the datagrams rx_reassembler delivered, grouped by channel with
+// both headers trimmed; no byte moves.  The reference verifies no UDP checksum
+// on rx; need = SCCSUM_ST_OK | SCCSUM_ST_L4_OK does.  Stateless apart from the
+// addresses it was made with.
+//   udp_rx rx(ports, host);
+//   rx.run(ip, d_status, nullptr, ip.n, out, d_ws, stream);       // out.first copied back: the channel bounds
+//   uint64_t q = udp_rx::taken(first[k + 1] - first[k], room);    // what the channel's queue accepts
+class udp_rx {
+    const udp_ports& _ports;
+    uint32_t _host;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() / run_reassembled() write (device arrays; sizes in <sccsum.h>, "UDP layer")
+    struct outputs {
+        uint8_t* cls = nullptr;        // n, optional
+        uint32_t* first = nullptr;     // channels + 2
+        uint32_t* order = nullptr;     // n
+        uint64_t* pay_off = nullptr;   // n (run() only)
+        uint32_t* pay_len = nullptr;   // n
+        uint32_t* src = nullptr;       // n
+        uint16_t* sport = nullptr;     // n
+    };
+
+    // what run_reassembled() reads of rx_reassembler's output
+    struct datagrams {
+        const sccsum_gather_desc* desc = nullptr;
+        const uint32_t* dgram_first = nullptr;  // m + 1
+        const uint64_t* dgram_off = nullptr;    // m
+        const uint32_t* dgram_len = nullptr;    // m
+        const uint32_t* dgram_head = nullptr;   // m
+        uint64_t m = 0;
+        const sccsum_frag_rec* rec = nullptr;   // the records reassembly took
+        uint64_t nrec = 0;
+    };
+
+    // host_address 0 accepts any destination; `ports` must outlive the object
+    udp_rx(const udp_ports& ports, uint32_t host_address) : _ports(ports), _host(host_address) {}
+
+    uint32_t host_address() const noexcept { return _host; }
+
+    static uint64_t workspace(uint64_t n) noexcept { return sccsum_udp_rx_workspace(n); }
+    static uint64_t reassembled_workspace(uint64_t m) noexcept { return sccsum_udp_rx_reasm_workspace(m); }
+
+    // _queue.push with `room` free slots keeps the first taken() datagrams of a channel's bucket (queue.hh:184-192)
+    static uint64_t taken(uint64_t count, uint64_t room) noexcept { return count < room ? count : room; }
+
+    // ip: an IPv4 bucket; d_status what the frames call wrote for it; d_index (may be null: frame j is
+    // batch frame j) the n batch frame indices of this call, e.g. a shard's slice of rx_steering's order
+    void run(const device_packet_batch& ip, const uint8_t* d_status, const uint32_t* d_index, uint64_t n,
+             const outputs& out, void* d_workspace, void* stream, uint32_t need = SCCSUM_ST_OK,
+             uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE | SCCSUM_ST_IPFRAG) const {
+        check(sccsum_udp_rx(ip.bytes, ip.bytes_len, ip.off, ip.len, ip.n, d_status, need, reject, _host, _ports.get(),
+                            d_index, n, out.cls, out.first, out.order, out.pay_off, out.pay_len, out.src, out.sport,
+                            d_workspace, stream),
+              "sccsum_udp_rx");
+    }
+
+    // d_l4_status: what spans_desc wrote for the datagrams' L4 verify, or null (the masks then 0)
+    void run_reassembled(const datagrams& in, const uint8_t* d_l4_status, const outputs& out, void* d_workspace,
+                         void* stream, uint32_t need = 0, uint32_t reject = 0) const {
+        check(sccsum_udp_rx_reasm(in.desc, in.dgram_first, in.dgram_off, in.dgram_len, in.dgram_head, in.m, in.rec,
+                                  in.nrec, d_l4_status, need, reject, _host, _ports.get(), out.cls, out.first,
+                                  out.order, out.pay_len, out.src, out.sport, d_workspace, stream),
+              "sccsum_udp_rx_reasm");
+    }
+};
+
+// UDP tx (<sccsum.h> sccsum_udp_send): ipv4_udp::send's header (udp.cc:175-197)
+// written into the 8 bytes of headroom in front of every payload, and the
+// spans and seeds of the checksum pass whose results tx_sender stores
+// (SCCSUM_SEND_L4); no payload byte moves.  Stateless.
+//   udp_tx tx({host, 1500, 0});
+//   tx.run(d_bytes, bytes_len, d_off, d_len, n, d_dst, d_dport, d_sport, out, stream);
+//   engine.sum_spans({d_bytes, bytes_len, out.l4_off, out.sum_len, n, 0}, out.seed, d_l4sum, ...);
+class udp_tx {
+    sccsum_udp_opts _opts;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays of n entries; <sccsum.h>, "UDP layer")
+    struct outputs {
+        uint64_t* l4_off = nullptr;
+        uint32_t* l4_len = nullptr;
+        uint32_t* sum_len = nullptr;
+        uint32_t* seed = nullptr;
+        uint8_t* proto = nullptr;       // optional
+        uint8_t* needs_csum = nullptr;
+        uint8_t* status = nullptr;
+    };
+
+    explicit udp_tx(const sccsum_udp_opts& opts) : _opts(opts) {}
+
+    const sccsum_udp_opts& opts() const noexcept { return _opts; }
+
+    // d_bytes is written: 8 bytes in front of every accepted payload
+    void run(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len, uint64_t n,
+             const uint32_t* d_dst, const uint16_t* d_dport, const uint16_t* d_sport, const outputs& out,
+             void* stream) const {
+        check(sccsum_udp_send(&_opts, d_bytes, bytes_len, d_off, d_len, d_dst, d_dport, d_sport, n, out.l4_off,
+                              out.l4_len, out.sum_len, out.seed, out.proto, out.needs_csum, out.status, stream),
+              "sccsum_udp_send");
     }
 };
 

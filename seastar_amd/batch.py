@@ -1288,6 +1288,348 @@ def eth_send(send, dst: torch.Tensor, table: ArpTable, hw_address, host: int, ne
                          keep=(send, dst))
 
 
+UDP_NEED = native.ST_OK                  # what ip.cc:121-144 lets through; the reference verifies no UDP checksum on rx
+UDP_REJECT = native.ST_MALFORMED | native.ST_RANGE | native.ST_IPFRAG
+
+
+class UdpPorts:
+    """sccsum_udp_ports_*: the immutable port -> channel table of the UDP layer
+    (include/sccsum.h, "UDP layer").  `ports` are distinct host-order ports,
+    at most 252; channel k is ports[k].  device=None makes a host-only table
+    (lookup alone).  A changed set of channels is a new object."""
+
+    def __init__(self, ports=(), device: int | None = 0):
+        self._lib = native.load()
+        self._h = None
+        ports = tuple(int(p) for p in ports)
+        if len(ports) > native.UDP_MAX_CHANNELS:
+            raise ValueError("ports: at most 252 channels")
+        if any(not 0 <= p <= 0xFFFF for p in ports) or len(set(ports)) != len(ports):
+            raise ValueError("ports: need distinct 16-bit values")
+        arr = (ctypes.c_uint16 * max(len(ports), 1))(*ports)
+        h = ctypes.c_void_p()
+        where = ctypes.addressof(arr) if ports else None
+        if device is None:
+            code = self._lib.sccsum_udp_ports_create_host(where, len(ports), ctypes.byref(h))
+        else:
+            code = self._lib.sccsum_udp_ports_create(int(device), where, len(ports), ctypes.byref(h))
+        native.check(code, "sccsum_udp_ports_create")
+        self._h = h
+        self.ports = ports
+        self.device = None if device is None else torch.device("cuda", int(device))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("UdpPorts is closed")
+        return self._h
+
+    @property
+    def channels(self) -> int:
+        return int(self._lib.sccsum_udp_ports_channels(self.handle))
+
+    def lookup(self, port: int):
+        """The channel bound to port, or None (host arithmetic)."""
+        k = int(self._lib.sccsum_udp_ports_lookup(self.handle, int(port) & 0xFFFF))
+        return None if k < 0 else k
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            native.check(self._lib.sccsum_udp_ports_destroy(h), "sccsum_udp_ports_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def _device_ports(ports, dev, what: str = "ports"):
+    if not isinstance(ports, UdpPorts):
+        raise ValueError(f"{what}: need a UdpPorts")
+    if ports.device != dev:
+        raise ValueError(f"{what}: the table lives on {ports.device}, the data on {dev}")
+    return ports.handle
+
+
+@dataclass
+class UdpRxResult:
+    """What sccsum_udp_rx / sccsum_udp_rx_reasm wrote (include/sccsum.h, "UDP
+    layer"): the call's frames (datagrams) grouped by channel, bucket
+    len(ports) everything dropped."""
+    source: object            # the frames batch, or the ReasmResult whose datagrams these are
+    ports: tuple
+    order: torch.Tensor       # int32 [n]: batch frame (datagram) indices grouped by bucket, arrival order inside one
+    first: torch.Tensor       # int32 [C + 2]: bucket bases, the last entry n
+    pay_off: torch.Tensor | None  # int64 [n], grouped order: off + 4 ihl + 8 (dropped: off); None for datagrams
+    pay_len: torch.Tensor     # int32 [n], grouped order (dropped: 0)
+    src_all: torch.Tensor     # int32 [n], grouped order: the source address
+    sport_all: torch.Tensor   # int16 [n], grouped order: the source port
+    cls: torch.Tensor | None  # uint8 [n], arrival order: k, or native.UDP_SKIP / UDP_SHORT / UDP_NOPORT
+    _bounds: np.ndarray | None = None
+
+    def bounds(self) -> np.ndarray:
+        """first on the host (synchronises once)."""
+        if self._bounds is None:
+            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        return self._bounds
+
+    def _range(self, k: int) -> tuple:
+        if not 0 <= int(k) <= len(self.ports):
+            raise ValueError(f"channel: need 0..{len(self.ports)}")
+        b = self.bounds()
+        return int(b[k]), int(b[k + 1])
+
+    def count(self, k: int) -> int:
+        a, e = self._range(k)
+        return e - a
+
+    def taken(self, k: int, room: int = native.UDP_QUEUE_SIZE) -> int:
+        """How many of channel k's datagrams _queue.push accepts with `room`
+        free slots: the partition is stable, so they are the first taken(k,
+        room) of the bucket (queue.hh:184-192)."""
+        if int(room) < 0:
+            raise ValueError("room: need >= 0")
+        return min(self.count(k), int(room))
+
+    def channel(self, k: int) -> PacketBatch:
+        """Channel k's payloads where they lie, a spans batch as it stands (no
+        copy).  Reassembled datagrams have no such batch: their payload is the
+        fragment list's bytes from +8 (indices(k), payload_len(k))."""
+        if self.pay_off is None:
+            raise ValueError("channel: reassembled datagrams are fragment lists; use indices(k) and payload_len(k)")
+        a, e = self._range(k)
+        ml = self.source.max_len
+        return PacketBatch(data=self.source.data, off=self.pay_off[a:e], length=self.pay_len[a:e],
+                           bytes_len=self.source.bytes_len, max_len=max(ml - 28, 0) if ml else 0)
+
+    def indices(self, k: int) -> torch.Tensor:
+        a, e = self._range(k)
+        return self.order[a:e]
+
+    def payload_len(self, k: int) -> torch.Tensor:
+        a, e = self._range(k)
+        return self.pay_len[a:e]
+
+    def src(self, k: int) -> torch.Tensor:
+        a, e = self._range(k)
+        return self.src_all[a:e]
+
+    def sport(self, k: int) -> torch.Tensor:
+        a, e = self._range(k)
+        return self.sport_all[a:e]
+
+
+def _udp_masks(host, need, reject) -> None:
+    for v, what in ((need, "need"), (reject, "reject")):
+        if not 0 <= int(v) <= 0xFF:
+            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+    if not 0 <= int(host) <= 0xFFFFFFFF:
+        raise ValueError("host: need a host-order IPv4 address, 0..2^32-1")
+
+
+def udp_rx_check(b: PacketBatch, status, ports, host, need, reject, index=None, cls=None) -> tuple:
+    """What udp_rx refuses before any launch; returns (n, nbatch)."""
+    if not isinstance(b, PacketBatch):
+        raise ValueError("b: need a PacketBatch of IPv4 frames (an eth_rx bucket)")
+    nbatch = b.n
+    if nbatch > 0xFFFFFFFF:
+        raise ValueError("b: at most 2^32-1 frames")
+    if not isinstance(status, torch.Tensor) or status.dim() != 1:
+        raise ValueError("status: need the 1-D uint8 tensor the frames call wrote, one entry per frame")
+    _need(status, nbatch, torch.uint8, "status", b.device)
+    _udp_masks(host, need, reject)
+    n = nbatch
+    if index is not None:
+        if not isinstance(index, torch.Tensor) or index.dim() != 1:
+            raise ValueError("index: need a 1-D int32 tensor of batch frame indices")
+        n = int(index.numel())
+        if n > 0xFFFFFFFF:
+            raise ValueError("index: at most 2^32-1 entries")
+        _need(index, n, torch.int32, "index", b.device)
+    if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
+        raise ValueError("cls: need a 1-D uint8 tensor of one entry per frame")
+    _need(cls, n, torch.uint8, "cls", b.device)
+    _device_ports(ports, b.device)
+    return n, nbatch
+
+
+def _udp_rx_outputs(n, channels, dev, stream, want_class, cls, with_off):
+    if cls is None and want_class:
+        cls = _scratch(max(n, 1), dev, stream, torch.uint8)
+    k = max(n, 1)
+    return dict(cls=cls, order=_scratch(k, dev, stream, torch.int32), first=_scratch(channels + 2, dev, stream, torch.int32),
+                pay_off=_scratch(k, dev, stream, torch.int64) if with_off else None,
+                pay_len=_scratch(k, dev, stream, torch.int32), src=_scratch(k, dev, stream, torch.int32),
+                sport=_scratch(k, dev, stream, torch.int16))
+
+
+def udp_rx(b: PacketBatch, status: torch.Tensor, ports: UdpPorts, host: int, need: int = UDP_NEED,
+           reject: int = UDP_REJECT, index: torch.Tensor | None = None, want_class: bool = True,
+           cls: torch.Tensor | None = None, stream=None) -> UdpRxResult:
+    """sccsum_udp_rx: the end of ipv4::handle_received_packet (ip.cc:159-162,
+    222-227) and ipv4_udp::received (udp.cc:45-53, 164-173) for the
+    non-fragment frames of an IPv4 bucket — for us? UDP? the trim to the IP
+    length, both headers dropped, the channel by destination port; a stable
+    partition by channel, no byte moves.
+
+        ip = eth_rx(wire).bucket(0)
+        status = torch.empty(ip.n, dtype=torch.uint8, device=dev)
+        ipv4_frames(ip, status=status)
+        r = udp_rx(ip, status, ports, me)             # index=: a shard's slice of Steer.run's order
+        spans(r.channel(k))                            # channel k's payloads, r.src(k), r.sport(k)
+        r.taken(k, room)                               # how many of them the channel's queue accepts
+
+    The reference verifies no UDP checksum on rx; need=ST_OK | ST_L4_OK does."""
+    lib = native.load()
+    n, nbatch = udp_rx_check(b, status, ports, host, need, reject, index, cls)
+    dev = b.device
+    t = _udp_rx_outputs(n, len(ports.ports), dev, stream, want_class, cls, True)
+    ws = _scratch(int(lib.sccsum_udp_rx_workspace(n)), dev, stream)
+    empty = nbatch == 0  # an empty tensor has no address
+    code = lib.sccsum_udp_rx(
+        ctypes_ptr(b.data), b.bytes_len, None if empty else ctypes_ptr(b.off), None if empty else ctypes_ptr(b.length),
+        nbatch, None if empty else ctypes_ptr(status), int(need), int(reject), int(host), ports.handle,
+        None if index is None or n == 0 else ctypes_ptr(index), n, _ptr(t["cls"]), ctypes_ptr(t["first"]),
+        ctypes_ptr(t["order"]), ctypes_ptr(t["pay_off"]), ctypes_ptr(t["pay_len"]), ctypes_ptr(t["src"]),
+        ctypes_ptr(t["sport"]), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_udp_rx")
+    return UdpRxResult(source=b, ports=ports.ports, order=t["order"][:n], first=t["first"], pay_off=t["pay_off"][:n],
+                       pay_len=t["pay_len"][:n], src_all=t["src"][:n], sport_all=t["sport"][:n],
+                       cls=None if t["cls"] is None else t["cls"][:n])
+
+
+def udp_rx_reasm_check(r, records, ports, host, l4_status, need, reject, cls=None) -> tuple:
+    """What udp_rx_reassembled refuses before any launch; returns (m, nrec):
+    the delivered datagrams (synchronises to count them) and the records."""
+    if not isinstance(r, ReasmResult):
+        raise ValueError("r: need the ReasmResult of reassemble()")
+    nrec = reasm_check(records, None, 0)
+    dev = records.device
+    m = r.totals()[0]
+    _udp_masks(host, need, reject)
+    if l4_status is None:
+        if int(need) or int(reject):
+            raise ValueError("need / reject: masks need l4_status")
+    else:
+        if not isinstance(l4_status, torch.Tensor) or l4_status.dim() != 1:
+            raise ValueError("l4_status: need the 1-D uint8 tensor spans_desc wrote, one entry per datagram")
+        _need(l4_status, m, torch.uint8, "l4_status", dev)
+    if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
+        raise ValueError("cls: need a 1-D uint8 tensor of one entry per datagram")
+    _need(cls, m, torch.uint8, "cls", dev)
+    _device_ports(ports, dev)
+    return m, nrec
+
+
+def udp_rx_reassembled(r: ReasmResult, records: torch.Tensor, ports: UdpPorts, host: int,
+                       l4_status: torch.Tensor | None = None, need: int = 0, reject: int = 0, want_class: bool = True,
+                       cls: torch.Tensor | None = None, stream=None) -> UdpRxResult:
+    """sccsum_udp_rx_reasm: udp_rx's demux for the datagrams reassemble()
+    delivered; `records` is the tensor reassemble() took.  The UDP header is
+    read through the fragment list; the payload is the list's bytes from +8.
+
+        r = reassemble(recs)
+        desc, first, off, length, seeds, max_len = r.lists()
+        st = torch.empty(off.numel(), dtype=torch.uint8, device=dev)
+        spans_desc(desc, first, off, length, max_len, seeds=seeds, status=st)
+        u = udp_rx_reassembled(r, recs, ports, me)     # l4_status=st, need=ST_OK: verified datagrams only
+        u.indices(k), u.payload_len(k), u.src(k), u.sport(k)
+    """
+    lib = native.load()
+    m, nrec = udp_rx_reasm_check(r, records, ports, host, l4_status, need, reject, cls)
+    dev = records.device
+    t = _udp_rx_outputs(m, len(ports.ports), dev, stream, want_class, cls, False)
+    ws = _scratch(int(lib.sccsum_udp_rx_reasm_workspace(m)), dev, stream)
+    empty = m == 0  # an empty tensor has no address
+    code = lib.sccsum_udp_rx_reasm(
+        None if empty else ctypes_ptr(r.desc), None if empty else ctypes_ptr(r.dgram_first),
+        None if empty else ctypes_ptr(r.dgram_off), None if empty else ctypes_ptr(r.dgram_len),
+        None if empty else ctypes_ptr(r.dgram_head), m, ctypes_ptr(records) if nrec else None, nrec,
+        None if empty else _ptr(l4_status), int(need), int(reject), int(host), ports.handle, _ptr(t["cls"]),
+        ctypes_ptr(t["first"]), ctypes_ptr(t["order"]), ctypes_ptr(t["pay_len"]), ctypes_ptr(t["src"]),
+        ctypes_ptr(t["sport"]), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_udp_rx_reasm")
+    return UdpRxResult(source=r, ports=ports.ports, order=t["order"][:m], first=t["first"], pay_off=None,
+                       pay_len=t["pay_len"][:m], src_all=t["src"][:m], sport_all=t["sport"][:m],
+                       cls=None if t["cls"] is None else t["cls"][:m])
+
+
+@dataclass
+class UdpSendResult:
+    """What sccsum_udp_send wrote (include/sccsum.h, "UDP layer"): the headers
+    lie in the payloads' headroom, in payloads.data itself."""
+    l4: PacketBatch            # header + payload per datagram: what ipv4_send takes
+    sum_batch: PacketBatch     # the spans whose results (with seeds) are ipv4_send's l4sum
+    seeds: torch.Tensor        # int32 [n]
+    proto: torch.Tensor        # uint8 [n]: 17
+    needs_csum: torch.Tensor   # uint8 [n]: offload_info::needs_csum
+    status: torch.Tensor       # uint8 [n]: native.ST_OK, or ST_RANGE / ST_MALFORMED (no header written)
+
+
+def udp_send_check(payloads: PacketBatch, dst, dport, sport, src_host, mtu, flags) -> int:
+    """What udp_send refuses before any launch; returns n."""
+    if not isinstance(payloads, PacketBatch):
+        raise ValueError("payloads: need a PacketBatch of UDP payloads, each with 8 bytes of headroom")
+    dev, n = payloads.device, payloads.n
+    if n > 0xFFFFFFFF:
+        raise ValueError("payloads: at most 2^32-1 datagrams")
+    if not 68 <= int(mtu) <= 65535:
+        raise ValueError(f"mtu: need 68..65535, got {mtu}")
+    if int(flags) & ~(native.UDP_CSUM_OFFLOAD | native.UDP_UFO):
+        raise ValueError(f"flags: unknown bits in {int(flags):#x}")
+    if not 0 <= int(src_host) <= 0xFFFFFFFF:
+        raise ValueError("src_host: need a host-order IPv4 address, 0..2^32-1")
+    for t, dtype, what in ((dst, torch.int32, "dst"), (dport, torch.int16, "dport"), (sport, torch.int16, "sport")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D {dtype} tensor of one entry per datagram")
+        _need(t, n, dtype, what, dev)
+    return n
+
+
+def udp_send(payloads: PacketBatch, dst: torch.Tensor, dport: torch.Tensor, sport: torch.Tensor, src_host: int,
+             mtu: int, flags: int = 0, stream=None) -> UdpSendResult:
+    """sccsum_udp_send: ipv4_udp::send's header (udp.cc:175-197) into the 8
+    bytes in front of every payload — the caller's headroom, which must not
+    overlap another payload — and the checksum pass's spans and seeds.
+
+        u = udp_send(payloads, dst, dport, sport, me, 1500)
+        l4sum = spans(u.sum_batch, seeds=u.seeds)
+        r = ipv4_send(u.l4, dst, u.proto, 1500, me, ids=ids, l4sum=l4sum, flags=native.SEND_L4)
+        ipv4_fill_desc(*r.lists()[:4], r.lists()[4], mode=native.FILL_IP)    # unless SEND computed it
+        wire = eth_send(r, dst, table, hw, me, netmask, gw).pack()
+
+    dst: int32 [n], dport / sport: int16 [n] (uint32 / uint16 values).  With
+    native.UDP_CSUM_OFFLOAD a datagram that needs no cut gets the folded
+    pseudo-header sum in its field and needs_csum = 1."""
+    lib = native.load()
+    n = udp_send_check(payloads, dst, dport, sport, src_host, mtu, flags)
+    dev = payloads.device
+    k = max(n, 1)
+    l4_off = _scratch(k, dev, stream, torch.int64)
+    l4_len = _scratch(k, dev, stream, torch.int32)
+    sum_len = _scratch(k, dev, stream, torch.int32)
+    seeds = _scratch(k, dev, stream, torch.int32)
+    proto = _scratch(k, dev, stream, torch.uint8)
+    needs_csum = _scratch(k, dev, stream, torch.uint8)
+    status = _scratch(k, dev, stream, torch.uint8)
+    opts = native.UdpOpts(int(src_host), int(mtu), int(flags))
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_udp_send(
+        ctypes.addressof(opts), ctypes_ptr(payloads.data), payloads.bytes_len,
+        None if empty else ctypes_ptr(payloads.off), None if empty else ctypes_ptr(payloads.length),
+        None if empty else ctypes_ptr(dst), None if empty else ctypes_ptr(dport), None if empty else ctypes_ptr(sport),
+        n, ctypes_ptr(l4_off), ctypes_ptr(l4_len), ctypes_ptr(sum_len), ctypes_ptr(seeds), ctypes_ptr(proto),
+        ctypes_ptr(needs_csum), ctypes_ptr(status), _stream(stream))
+    native.check(code, "sccsum_udp_send")
+    ml = payloads.max_len + native.UDP_HDR if payloads.max_len else 0
+    l4 = PacketBatch(data=payloads.data, off=l4_off[:n], length=l4_len[:n], bytes_len=payloads.bytes_len, max_len=ml)
+    sums = PacketBatch(data=payloads.data, off=l4_off[:n], length=sum_len[:n], bytes_len=payloads.bytes_len, max_len=ml)
+    return UdpSendResult(l4=l4, sum_batch=sums, seeds=seeds[:n], proto=proto[:n], needs_csum=needs_csum[:n],
+                         status=status[:n])
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

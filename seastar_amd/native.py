@@ -150,6 +150,19 @@ _PROTOS = {
     "sccsum_eth_send_workspace": (_u64, [_u64]),
     "sccsum_eth_send": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sccsum_udp_ports_create": (ctypes.c_int, [ctypes.c_int, _vp, _u32, ctypes.POINTER(_vp)]),
+    "sccsum_udp_ports_create_host": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(_vp)]),
+    "sccsum_udp_ports_destroy": (ctypes.c_int, [_vp]),
+    "sccsum_udp_ports_lookup": (ctypes.c_int, [_vp, ctypes.c_uint16]),
+    "sccsum_udp_ports_channels": (_u32, [_vp]),
+    "sccsum_udp_rx_workspace": (_u64, [_u64]),
+    "sccsum_udp_rx": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sccsum_udp_rx_reasm_workspace": (_u64, [_u64]),
+    "sccsum_udp_rx_reasm": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sccsum_udp_send": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -245,6 +258,22 @@ class EthOpts(ctypes.Structure):
     """sccsum_eth_opts: what eth_send takes from the interface and its ipv4 (addresses in host order)."""
     _fields_ = [("hw_address", ctypes.c_uint64), ("host", ctypes.c_uint32), ("netmask", ctypes.c_uint32),
                 ("gw", ctypes.c_uint32), ("eth_proto", ctypes.c_uint16)]
+
+
+UDP_NOPORT = 0xFF     # udp_rx classes of dropped frames / datagrams
+UDP_SHORT = 0xFE
+UDP_SKIP = 0xFD
+UDP_MAX_CHANNELS = 252
+UDP_HDR = 8           # sizeof(udp_hdr)
+UDP_CSUM_OFFLOAD = 0x01
+UDP_UFO = 0x02
+UDP_PAYLOAD_MAX = SEND_L4_MAX - UDP_HDR  # 65507
+UDP_QUEUE_SIZE = 1024  # ipv4_udp::default_queue_size
+
+
+class UdpOpts(ctypes.Structure):
+    """sccsum_udp_opts: what ipv4_udp::send takes from its ipv4 (source address, MTU, offload flags)."""
+    _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class Fragment(ctypes.Structure):
