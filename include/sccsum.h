@@ -1364,6 +1364,223 @@ int sccsum_udp_send(const sccsum_udp_opts* opts, void* d_bytes, uint64_t bytes_l
                     uint64_t n, uint64_t* d_l4_off, uint32_t* d_l4_len, uint32_t* d_sum_len, uint32_t* d_seed,
                     uint8_t* d_proto, uint8_t* d_needs_csum, uint8_t* d_status, void* stream);
 
+/* ---- TCP layer: rx demux by connection, resets, tx headers in headroom ----------------
+ * The stateless per-segment TCP steps of the reference above the IPv4 layer,
+ * for a whole batch on the device (paths relative to the reference tree):
+ *   ipv4::handle_received_packet, its end   src/net/ip.cc:159-162, 222-227        \
+ *   tcp::received, before any tcb is touched  include/seastar/net/tcp.hh:865-942   > sccsum_tcp_rx
+ *   tcp::respond_with_reset                 tcp.hh:981-1023                        /
+ *   tcp_hdr::read / write                   tcp.hh:246-282
+ *   tcb::output_one, its header             tcp.hh:1620-1698                         sccsum_tcp_send
+ * The state machine (input_handle_*_state, timers, retransmit, option
+ * negotiation) stays on the host; it runs per connection over a contiguous slice
+ * of parsed records.  No payload byte moves and no atomic decides a position:
+ * two runs give identical bytes; plain dependent launches on `stream`, no
+ * allocation, no memset, no host synchronisation; capturable.  Addresses and
+ * ports are in host order.
+ *
+ * Connection table.  An immutable device object (like sccsum_arp_table: a
+ * changed set of connections is a new object, the old one destroyed once its
+ * stream is synchronised).  conns[nconns] are HOST memory, nconns <=
+ * SCCSUM_TCP_MAX_CONNS (2^20; conns may be NULL when nconns == 0); connection c
+ * is conns[c], what tcp::_tcbs maps for that connid whatever its state: a
+ * SYN_SENT tcb is an entry like any other, the split of tcp.hh:932-940 is the
+ * host's, per connection.  listen[nlisten] are the distinct ports of
+ * tcp::_listening, nlisten <= 65 536.  The device form of the connections is
+ * open addressing with linear probing over 2^bits 16-byte slots {local_ip,
+ * foreign_ip, local_port << 16 | foreign_port, c + 1} (0 in the last word:
+ * empty), 2^bits the smallest power of two >= max(16, 2 nconns): a probe is one
+ * 16-byte load, and any 96-bit key is valid, all zeros included.  The home slot
+ * is an fmix32-style mix of the three key words, which sccsum_tcp_conns_slot
+ * exports (its low `bits` bits).  The listening ports are a 65 536-entry byte
+ * table.  create leaves the caller's current device alone; SCCSUM_EINVAL for
+ * out == NULL, a NULL array with a nonzero count, a count past its limit, a
+ * connid given twice (a map has no duplicate keys) or a port given twice, before
+ * the device is looked at; SCCSUM_ENODEV for a device index out of range.
+ * _lookup (the index, or -1; -1 for a NULL table) and _listening (1 / 0) are
+ * host arithmetic on the object's own copy; _bits and _count are 0 for NULL.
+ * _create_host makes the same object without a device copy, for lookup alone:
+ * the device calls refuse it with SCCSUM_ENODEV after their argument checks.
+ *
+ * sccsum_tcp_rx: the non-fragment frames of an IPv4 bucket; the input is exactly
+ * what sccsum_udp_rx takes (the frames batch, d_status[nbatch], the masks need /
+ * reject, host_address with 0 accepting any destination, d_index[n] or NULL with
+ * n <= nbatch).  The documented default is need = SCCSUM_ST_OK | SCCSUM_ST_L4_OK,
+ * reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE | SCCSUM_ST_IPFRAG: unlike UDP
+ * the reference does verify the TCP checksum on rx (tcp.hh:876-883); a caller
+ * with rx_csum_offload drops SCCSUM_ST_L4_OK from need.
+ *   Class of frame j (d_class[n], optional, in the call's order), with E =
+ * ip_len - 4 ihl (the L4 length after the trims of ip.cc:134-136, 225) and H = 4
+ * * (byte 12 of the L4 >> 4), decided in this order:
+ *   SCCSUM_TCP_SKIP    sccsum_udp_rx's SKIP rules word for word, with protocol != 6
+ *   SCCSUM_TCP_SHORT   E < 20 (tcp.hh:866-869) or H < 20 (tcp.hh:871-874): both
+ *                      silent drops in the reference
+ *   SCCSUM_TCP_CONN    the connid {dst, src, dport, sport} (tcp.hh:885) is in the
+ *                      table, and H <= E
+ *   SCCSUM_TCP_LISTEN  not in the table, dport is listening, and H <= E
+ *   SCCSUM_TCP_SHORT   in the table or listening, and H > E: the options are not
+ *                      inside the segment.  The reference's trim_front(H) /
+ *                      get_header(0, H) asserts or yields null there
+ *                      (tcp.hh:1117-1119, 1216); here the frame is dropped
+ *   SCCSUM_TCP_RESET   no connection, no listener, RST clear: respond_with_reset
+ *                      (tcp.hh:898).  H > E does not matter: the reference reads
+ *                      only the twenty fixed bytes
+ *   SCCSUM_TCP_NOCONN  no connection, no listener, RST set: discarded (tcp.hh:983-985)
+ * Everything order-dependent — listener->full(), a new tcb that a later segment
+ * of the same batch would find, the RST / ACK / SYN triage of tcp.hh:900-929 —
+ * lands in the LISTEN bucket in arrival order, for the host to walk with its
+ * real _tcbs: every segment of a connid that is not in the table but whose port
+ * listens reaches the host in arrival order, so no outcome depends on the
+ * device's view being stale.
+ *   d_first[5]   bucket bases: bucket 0 CONN, 1 LISTEN, 2 RESET, 3 everything
+ *                dropped (NOCONN, SHORT, SKIP); the last entry n
+ *   d_order[n]   batch frame indices grouped by bucket.  Inside bucket 0 by
+ *                ascending connection index, the call's order inside a
+ *                connection (a STABLE sort: a connection's segments reach its tcb
+ *                in arrival order); buckets 1 to 3 are stable partitions
+ *   d_seg[n]     one sccsum_tcp_seg per position of d_order, 8-byte aligned.
+ *                Classes CONN, LISTEN, RESET, NOCONN: pay_off = off + 4 ihl + H
+ *                (the options are the H - 20 bytes before it), pay_len = E - H
+ *                (seg_len of tcp.hh:1221 before SYN / FIN are counted; 0 where H
+ *                > E), the twenty fixed bytes parsed; conn the connection index
+ *                in bucket 0, UINT32_MAX elsewhere.  SKIP and SHORT: pay_off =
+ *                off (0 when the index is out of range), conn = UINT32_MAX, all
+ *                other fields 0
+ *   d_src[n]     the source addresses in grouped order, 0 for SKIP and SHORT
+ *   d_run_conn[R], d_run_first[R + 1]   the runs of bucket 0: run r is connection
+ *                d_run_conn[r], positions d_run_first[r] .. d_run_first[r + 1]
+ *                of d_order / d_seg (the closing entry is d_first[1]); each array
+ *                has room for min(n, nconns) + 1 entries.  A connection's slice
+ *                of d_seg is d_seg + d_run_first[r], and its pay_off / pay_len
+ *                are a spans batch
+ *   d_rst, d_rst_dst   the r-th segment of bucket 2 is answered at d_rst[20 r ..
+ *                + 20) as respond_with_reset writes it: ports swapped; seq =
+ *                SEG.ACK when ACK is set, else 0; with SYN set ack = SEG.SEQ + 1
+ *                and the ACK flag; RST set, data_offset 5, window and urgent 0.
+ *                The checksum field is the full checksum (pseudo-header {local =
+ *                dst, foreign = src, 6, 20} plus the twenty bytes), or with
+ *                `flags` = SCCSUM_TCP_CSUM_OFFLOAD the folded pseudo-header sum,
+ *                not complemented.  d_rst_dst[r] is the foreign address.  d_rst
+ *                (room for 20 n bytes, 4-byte aligned), offsets 20 r, lengths 20,
+ *                protocol 6 and d_rst_dst are an L4 batch for sccsum_ipv4_send as
+ *                they stand, without SCCSUM_SEND_L4.  send_packet_without_tcb
+ *                drops what does not fit _queue_space (tcp.hh:946-953): the list
+ *                is stable, so that is the first min(count, space / 20) entries,
+ *                host arithmetic the wrappers offer as taken(space)
+ *   d_total[4]   {R, resets, 0, 0}, 8-byte aligned
+ * The decode kernel reads every frame once and leaves its record and a sort key
+ * in the workspace; the key is the connection index for bucket 0 and nconns + 0
+ * / 1 / 2 for buckets 1 to 3, so one stable LSD radix sort in 8-bit digits
+ * yields the grouped order and the bucket bases: one pass up to 253 connections,
+ * two up to 65 533, three beyond.  d_workspace: sccsum_tcp_rx_workspace(n,
+ * nconns) bytes, 16-byte aligned.  n, nbatch <= 2^32 - 1.  n == 0 writes d_first
+ * and d_total (all 0) and d_run_first[0], and is SCCSUM_OK; the other arrays may
+ * then be NULL.
+ *
+ * sccsum_tcp_send: output_one's header for n segments.  Payload i is
+ * d_bytes[d_off[i] .. + d_len[i]) and the d_out[i].hdr_len bytes in front of it
+ * (20..60, a multiple of 4) belong to the call; the caller has already written
+ * the option bytes at [d_off - hdr_len + 20, d_off) (tcp_option::fill, SYN
+ * segments only).  The call writes the twenty fixed bytes at d_off - hdr_len as
+ * tcp_hdr::write does: ports, seq, ack, data_offset = hdr_len / 4, the flags
+ * byte as given, window, checksum 0, urgent 0, and
+ *   d_l4_off = d_off - hdr_len, d_l4_len = d_len + hdr_len, d_proto = 6 (optional)
+ *   d_sum_len, d_seed   the spans batch whose sccsum_spans results
+ *                       sccsum_ipv4_send(SCCSUM_SEND_L4) stores at TCP +16
+ *   d_needs_csum (u8), d_tso_seg (u16)   offload_info::needs_csum, tso_seg_size
+ * The three forms of tcp.hh:1662-1694.  Full: d_sum_len = d_l4_len, d_seed =
+ * sccsum_pseudo_seed(src, dst, 6, d_l4_len).  SCCSUM_TCP_CSUM_OFFLOAD: d_sum_len
+ * = 0, d_seed = 0xFFFF ^ sccsum_pseudo_seed(src, dst, 6, d_l4_len), so the empty
+ * span's result is the folded pseudo-header sum, and d_needs_csum = 1.
+ * SCCSUM_TCP_CSUM_OFFLOAD | SCCSUM_TCP_TSO with d_len > mss: the same with the
+ * pseudo-header's length 0, and d_tso_seg = mss; d_tso_seg = 0 otherwise
+ * (SCCSUM_TCP_TSO without the offload flag changes nothing, as in the reference).
+ *   d_status[n] (required): SCCSUM_ST_OK; SCCSUM_ST_RANGE: d_off < hdr_len (as
+ * given) or [d_off, d_off + d_len) is not inside [0, bytes_len) (64-bit test);
+ * SCCSUM_ST_MALFORMED: hdr_len outside 20..60 or not a multiple of 4, d_len +
+ * hdr_len > 65 515, SCCSUM_TCP_TSO with mss == 0; both bits when both hold.  A
+ * refused segment writes nothing into d_bytes and gets d_l4_off = UINT64_MAX,
+ * d_l4_len = d_sum_len = d_seed = 0, d_tso_seg = 0, d_needs_csum = 0; d_proto,
+ * where given, is 6 for every segment, refused ones included (as
+ * sccsum_udp_send writes its 17): sccsum_ipv4_send refuses the segment by its
+ * offset, whatever the protocol says.  opts: the
+ * source address, the MTU (68..65535) and SCCSUM_TCP_* flags.  One elementwise
+ * kernel; n <= 2^32 - 1; n == 0 is SCCSUM_OK.
+ *
+ * No output array may overlap another output array, an input or the workspace:
+ * the launches of one call read what earlier ones wrote (sccsum_tcp_rx's reset
+ * kernel reads d_seg, d_first and the workspace; the run kernels read d_first),
+ * so an aliased array gives wrong results without an error.  The call does not
+ * check this.
+ *
+ * Alignment: d_off, d_seg, d_l4_off, d_total 8 bytes; the 32-bit arrays, d_rst
+ * and d_out 4; the 16-bit arrays 2; d_bytes any.  SCCSUM_EINVAL before any
+ * device work, in every call: a NULL required pointer, misalignment, a NULL
+ * table, mask bits past 0xFF, n / nbatch out of range, n > nbatch without
+ * d_index, mtu outside 68..65535, unknown flags, a stream of another device than
+ * the table's (tcp_send: than the current one). */
+#define SCCSUM_TCP_CONN   0x00u
+#define SCCSUM_TCP_LISTEN 0x01u
+#define SCCSUM_TCP_RESET  0x02u
+#define SCCSUM_TCP_NOCONN 0x03u
+#define SCCSUM_TCP_SHORT  0xFEu
+#define SCCSUM_TCP_SKIP   0xFDu
+#define SCCSUM_TCP_MAX_CONNS (1u << 20)
+#define SCCSUM_TCP_CSUM_OFFLOAD 0x01u /* hw_features().tx_csum_l4_offload (tcp.hh:1008, 1662) */
+#define SCCSUM_TCP_TSO          0x02u /* hw_features().tx_tso (tcp.hh:1674) */
+
+typedef struct sccsum_tcp_conns sccsum_tcp_conns;
+typedef struct sccsum_tcp_conn {
+    uint32_t local_ip, foreign_ip;
+    uint16_t local_port, foreign_port;
+} sccsum_tcp_conn;
+typedef struct sccsum_tcp_seg {
+    uint64_t pay_off; /* off + 4 ihl + H: the bytes behind the header */
+    uint32_t pay_len; /* E - H */
+    uint32_t seq, ack; /* host order */
+    uint32_t conn;    /* connection index; UINT32_MAX outside bucket 0 */
+    uint16_t window, sport, dport;
+    uint8_t flags;    /* byte 13 of the header as it stands: FIN 1, SYN 2, RST 4, PSH 8, ACK 16, URG 32 */
+    uint8_t hdr_len;  /* H */
+} sccsum_tcp_seg;
+typedef struct sccsum_tcp_out {
+    uint32_t dst, seq, ack;
+    uint16_t sport, dport, window;
+    uint8_t flags, hdr_len;
+    uint32_t mss;     /* _snd.mss: consulted with SCCSUM_TCP_TSO */
+} sccsum_tcp_out;
+typedef struct sccsum_tcp_opts {
+    uint32_t src_host; /* ipv4::_host_address, host order */
+    uint32_t mtu;      /* hw_features().mtu, 68..65535 */
+    uint32_t flags;
+} sccsum_tcp_opts;
+
+int sccsum_tcp_conns_create(int device, const sccsum_tcp_conn* conns, uint32_t nconns, const uint16_t* listen,
+                            uint32_t nlisten, sccsum_tcp_conns** out);
+int sccsum_tcp_conns_create_host(const sccsum_tcp_conn* conns, uint32_t nconns, const uint16_t* listen,
+                                 uint32_t nlisten, sccsum_tcp_conns** out);
+int sccsum_tcp_conns_destroy(sccsum_tcp_conns* t);
+int64_t sccsum_tcp_conns_lookup(const sccsum_tcp_conns* t, uint32_t local_ip, uint32_t foreign_ip, uint16_t local_port,
+                                uint16_t foreign_port);
+int sccsum_tcp_conns_listening(const sccsum_tcp_conns* t, uint16_t port);
+uint32_t sccsum_tcp_conns_slot(uint32_t local_ip, uint32_t foreign_ip, uint16_t local_port, uint16_t foreign_port,
+                               uint32_t bits);
+uint32_t sccsum_tcp_conns_bits(const sccsum_tcp_conns* t);
+uint32_t sccsum_tcp_conns_count(const sccsum_tcp_conns* t);
+
+uint64_t sccsum_tcp_rx_workspace(uint64_t n, uint32_t nconns);
+int sccsum_tcp_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
+                  uint64_t nbatch, const uint8_t* d_status, uint32_t need, uint32_t reject, uint32_t host_address,
+                  const sccsum_tcp_conns* conns, const uint32_t* d_index, uint64_t n, uint32_t flags, uint8_t* d_class,
+                  uint32_t* d_first, uint32_t* d_order, sccsum_tcp_seg* d_seg, uint32_t* d_src, uint32_t* d_run_conn,
+                  uint32_t* d_run_first, void* d_rst, uint32_t* d_rst_dst, uint64_t* d_total, void* d_workspace,
+                  void* stream);
+
+int sccsum_tcp_send(const sccsum_tcp_opts* opts, void* d_bytes, uint64_t bytes_len, const uint64_t* d_off,
+                    const uint32_t* d_len, const sccsum_tcp_out* d_out, uint64_t n, uint64_t* d_l4_off,
+                    uint32_t* d_l4_len, uint32_t* d_sum_len, uint32_t* d_seed, uint16_t* d_tso_seg, uint8_t* d_proto,
+                    uint8_t* d_needs_csum, uint8_t* d_status, void* stream);
+
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);
 int sccsum_host_free(void* p);

@@ -829,6 +829,151 @@ public:
     }
 };
 
+// TCP connection table (<sccsum.h> sccsum_tcp_conns_*): an immutable device
+// copy of what tcp::_tcbs maps (tcp.hh:885-886) and of the ports of
+// tcp::_listening: connection c is conns[c], whatever its state.  A changed
+// set of connections is a new object; the old one is destroyed once its
+// stream is synchronised.
+//   const sccsum_tcp_conn c[] = {{me, peer, 80, 40000}};
+//   const uint16_t listening[] = {80};
+//   tcp_conns conns(gpu, c, 1, listening, 1);
+class tcp_conns {
+    sccsum_tcp_conns* _t = nullptr;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // conns, listen: host memory, distinct, host order; nconns <= SCCSUM_TCP_MAX_CONNS, nlisten <= 65536
+    tcp_conns(int device, const sccsum_tcp_conn* conns, uint32_t nconns, const uint16_t* listen, uint32_t nlisten) {
+        check(sccsum_tcp_conns_create(device, conns, nconns, listen, nlisten, &_t), "sccsum_tcp_conns_create");
+    }
+    // no device copy: lookup() and listening() alone
+    tcp_conns(const sccsum_tcp_conn* conns, uint32_t nconns, const uint16_t* listen, uint32_t nlisten) {
+        check(sccsum_tcp_conns_create_host(conns, nconns, listen, nlisten, &_t), "sccsum_tcp_conns_create_host");
+    }
+    tcp_conns(const tcp_conns&) = delete;
+    tcp_conns& operator=(const tcp_conns&) = delete;
+    ~tcp_conns() { sccsum_tcp_conns_destroy(_t); }
+
+    const sccsum_tcp_conns* get() const noexcept { return _t; }
+    uint32_t count() const noexcept { return sccsum_tcp_conns_count(_t); }
+    uint32_t bits() const noexcept { return sccsum_tcp_conns_bits(_t); }
+
+    // host arithmetic: the connection of a connid, or -1; is the port listening
+    int64_t lookup(const sccsum_tcp_conn& id) const noexcept {
+        return sccsum_tcp_conns_lookup(_t, id.local_ip, id.foreign_ip, id.local_port, id.foreign_port);
+    }
+    bool listening(uint16_t port) const noexcept { return sccsum_tcp_conns_listening(_t, port) != 0; }
+    // the home slot of a connid in a table of 2^bits slots
+    static uint32_t slot(const sccsum_tcp_conn& id, uint32_t bits) noexcept {
+        return sccsum_tcp_conns_slot(id.local_ip, id.foreign_ip, id.local_port, id.foreign_port, bits);
+    }
+};
+
+// TCP rx (<sccsum.h> sccsum_tcp_rx): the stateless part of tcp::received
+// (tcp.hh:865-942) for the non-fragment frames of an IPv4 bucket — the header
+// parsed, the connid looked up, then the listening ports, then the RST of
+// respond_with_reset (tcp.hh:981-1023) — ending in segments grouped per
+// connection in arrival order; no byte moves.  The state machine stays the
+// caller's, per connection.  Stateless apart from what it was made with.
+//   tcp_rx rx(conns, host);
+//   rx.run(ip, d_status, nullptr, ip.n, out, d_ws, stream);      // out.first, out.total copied back
+//   uint64_t q = tcp_rx::taken(total[1], queue_space);           // the answers send_packet_without_tcb accepts
+class tcp_rx {
+    const tcp_conns& _conns;
+    uint32_t _host;
+    uint32_t _flags;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays; sizes in <sccsum.h>, "TCP layer")
+    struct outputs {
+        uint8_t* cls = nullptr;          // n, optional
+        uint32_t* first = nullptr;       // 5
+        uint32_t* order = nullptr;       // n
+        sccsum_tcp_seg* seg = nullptr;   // n
+        uint32_t* src = nullptr;         // n
+        uint32_t* run_conn = nullptr;    // min(n, count) + 1
+        uint32_t* run_first = nullptr;   // min(n, count) + 1
+        void* rst = nullptr;             // 20 n bytes
+        uint32_t* rst_dst = nullptr;     // n
+        uint64_t* total = nullptr;       // 4: R, resets
+    };
+
+    // host_address 0 accepts any destination; flags: SCCSUM_TCP_CSUM_OFFLOAD for the answers; `conns` must outlive the object
+    tcp_rx(const tcp_conns& conns, uint32_t host_address, uint32_t flags = 0)
+        : _conns(conns), _host(host_address), _flags(flags) {}
+
+    uint32_t host_address() const noexcept { return _host; }
+
+    uint64_t workspace(uint64_t n) const noexcept { return sccsum_tcp_rx_workspace(n, _conns.count()); }
+
+    // send_packet_without_tcb with `space` bytes of _queue_space keeps the first taken() answers (tcp.hh:946-953)
+    static uint64_t taken(uint64_t resets, uint64_t space) noexcept { return resets < space / 20 ? resets : space / 20; }
+
+    // ip: an IPv4 bucket; d_status what the frames call wrote for it; d_index (may be null: frame j is
+    // batch frame j) the n batch frame indices of this call, e.g. a shard's slice of rx_steering's order
+    void run(const device_packet_batch& ip, const uint8_t* d_status, const uint32_t* d_index, uint64_t n,
+             const outputs& out, void* d_workspace, void* stream, uint32_t need = SCCSUM_ST_OK | SCCSUM_ST_L4_OK,
+             uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE | SCCSUM_ST_IPFRAG) const {
+        check(sccsum_tcp_rx(ip.bytes, ip.bytes_len, ip.off, ip.len, ip.n, d_status, need, reject, _host, _conns.get(),
+                            d_index, n, _flags, out.cls, out.first, out.order, out.seg, out.src, out.run_conn,
+                            out.run_first, out.rst, out.rst_dst, out.total, d_workspace, stream),
+              "sccsum_tcp_rx");
+    }
+};
+
+// TCP tx (<sccsum.h> sccsum_tcp_send): tcb::output_one's header (tcp.hh:1620-1698)
+// written into the hdr_len bytes of headroom in front of every payload, the
+// caller's options behind it, and the spans and seeds of the checksum pass
+// whose results tx_sender stores (SCCSUM_SEND_L4); no payload byte moves.
+//   tcp_tx tx({host, 1500, 0});
+//   tx.run(d_bytes, bytes_len, d_off, d_len, d_out, n, out, stream);
+//   engine.sum_spans({d_bytes, bytes_len, out.l4_off, out.sum_len, n, 0}, out.seed, d_l4sum, ...);
+class tcp_tx {
+    sccsum_tcp_opts _opts;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays of n entries; <sccsum.h>, "TCP layer")
+    struct outputs {
+        uint64_t* l4_off = nullptr;
+        uint32_t* l4_len = nullptr;
+        uint32_t* sum_len = nullptr;
+        uint32_t* seed = nullptr;
+        uint16_t* tso_seg = nullptr;
+        uint8_t* proto = nullptr;       // optional
+        uint8_t* needs_csum = nullptr;
+        uint8_t* status = nullptr;
+    };
+
+    explicit tcp_tx(const sccsum_tcp_opts& opts) : _opts(opts) {}
+
+    const sccsum_tcp_opts& opts() const noexcept { return _opts; }
+
+    // d_bytes is written: the twenty fixed bytes at d_off - hdr_len of every accepted segment
+    void run(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
+             const sccsum_tcp_out* d_out, uint64_t n, const outputs& out, void* stream) const {
+        check(sccsum_tcp_send(&_opts, d_bytes, bytes_len, d_off, d_len, d_out, n, out.l4_off, out.l4_len, out.sum_len,
+                              out.seed, out.tso_seg, out.proto, out.needs_csum, out.status, stream),
+              "sccsum_tcp_send");
+    }
+};
+
 }  // namespace net
 
 }  // namespace seastar

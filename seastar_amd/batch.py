@@ -1630,6 +1630,309 @@ def udp_send(payloads: PacketBatch, dst: torch.Tensor, dport: torch.Tensor, spor
                          status=status[:n])
 
 
+TCP_NEED = native.ST_OK | native.ST_L4_OK   # the reference verifies the TCP checksum on rx (tcp.hh:876-883)
+TCP_REJECT = native.ST_MALFORMED | native.ST_RANGE | native.ST_IPFRAG
+TCP_SEG_DTYPE = np.dtype([("pay_off", "<u8"), ("pay_len", "<u4"), ("seq", "<u4"), ("ack", "<u4"), ("conn", "<u4"),
+                          ("window", "<u2"), ("sport", "<u2"), ("dport", "<u2"), ("flags", "u1"), ("hdr_len", "u1")])
+TCP_OUT_DTYPE = np.dtype([("dst", "<u4"), ("seq", "<u4"), ("ack", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
+                          ("window", "<u2"), ("flags", "u1"), ("hdr_len", "u1"), ("mss", "<u4")])
+
+
+class TcpConns:
+    """sccsum_tcp_conns_*: the immutable connection table of the TCP layer
+    (include/sccsum.h, "TCP layer").  `conns` are distinct (local_ip,
+    foreign_ip, local_port, foreign_port) in host order, at most 2^20;
+    connection c is conns[c].  `listen` are the distinct listening ports.
+    device=None makes a host-only table (lookup alone).  A changed set of
+    connections is a new object."""
+
+    def __init__(self, conns=(), listen=(), device: int | None = 0):
+        self._lib = native.load()
+        self._h = None
+        arr = np.asarray(conns, dtype=np.int64).reshape(-1, 4)
+        listen = np.asarray(listen, dtype=np.int64).reshape(-1)
+        if arr.shape[0] > native.TCP_MAX_CONNS:
+            raise ValueError("conns: at most 2^20 connections")
+        if arr.size and (arr.min() < 0 or arr[:, :2].max() > 0xFFFFFFFF or arr[:, 2:].max() > 0xFFFF):
+            raise ValueError("conns: need (local_ip, foreign_ip, local_port, foreign_port), 32- and 16-bit values")
+        if listen.size > 65536 or (listen.size and (listen.min() < 0 or listen.max() > 0xFFFF)):
+            raise ValueError("listen: need at most 65536 16-bit ports")
+        if np.unique(listen).size != listen.size:
+            raise ValueError("listen: need distinct ports")
+        packed = np.zeros(max(arr.shape[0], 1), dtype=np.dtype([("l", "<u4"), ("f", "<u4"), ("lp", "<u2"), ("fp", "<u2")]))
+        if arr.shape[0]:
+            packed["l"], packed["f"], packed["lp"], packed["fp"] = arr[:, 0], arr[:, 1], arr[:, 2], arr[:, 3]
+        ports = np.ascontiguousarray(listen.astype(np.uint16)) if listen.size else np.zeros(1, np.uint16)
+        h = ctypes.c_void_p()
+        a = packed.ctypes.data if arr.shape[0] else None
+        b = ports.ctypes.data if listen.size else None
+        if device is None:
+            code = self._lib.sccsum_tcp_conns_create_host(a, arr.shape[0], b, listen.size, ctypes.byref(h))
+        else:
+            code = self._lib.sccsum_tcp_conns_create(int(device), a, arr.shape[0], b, listen.size, ctypes.byref(h))
+        # every other cause of SCCSUM_EINVAL (a count past its limit, a value out of range, a port given
+        # twice) was refused above, so what is left is a connid given twice; a check dropped above
+        # would make this message wrong
+        if code == native.SCCSUM_EINVAL:
+            raise ValueError("conns: a connection given twice")
+        native.check(code, "sccsum_tcp_conns_create")
+        self._h = h
+        self.nconns = int(arr.shape[0])
+        self.device = None if device is None else torch.device("cuda", int(device))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("TcpConns is closed")
+        return self._h
+
+    @property
+    def count(self) -> int:
+        return int(self._lib.sccsum_tcp_conns_count(self.handle))
+
+    @property
+    def bits(self) -> int:
+        return int(self._lib.sccsum_tcp_conns_bits(self.handle))
+
+    def lookup(self, local_ip: int, foreign_ip: int, local_port: int, foreign_port: int):
+        """The connection of a connid, or None (host arithmetic)."""
+        c = int(self._lib.sccsum_tcp_conns_lookup(self.handle, int(local_ip) & 0xFFFFFFFF, int(foreign_ip) & 0xFFFFFFFF,
+                                                  int(local_port) & 0xFFFF, int(foreign_port) & 0xFFFF))
+        return None if c < 0 else c
+
+    def listening(self, port: int) -> bool:
+        return bool(self._lib.sccsum_tcp_conns_listening(self.handle, int(port) & 0xFFFF))
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            native.check(self._lib.sccsum_tcp_conns_destroy(h), "sccsum_tcp_conns_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+@dataclass
+class TcpRxResult:
+    """What sccsum_tcp_rx wrote (include/sccsum.h, "TCP layer"): the call's
+    segments grouped by bucket (0 a known connection, 1 a listening port, 2
+    answered with a RST, 3 dropped), bucket 0 by connection."""
+    source: PacketBatch
+    order: torch.Tensor       # int32 [n]: batch frame indices in grouped order
+    first: torch.Tensor       # int32 [5]: bucket bases, the last entry n
+    seg: torch.Tensor         # uint8 [n, 32]: sccsum_tcp_seg records, grouped order (TCP_SEG_DTYPE on the host)
+    src_all: torch.Tensor     # int32 [n], grouped order: the source address
+    run_conn: torch.Tensor    # int32 [>= R]: the connection of run r
+    run_first: torch.Tensor   # int32 [>= R + 1]: where run r starts in bucket 0
+    rst: torch.Tensor         # uint8 [>= 20 n]: the RST answers of bucket 2, 20 bytes each
+    rst_dst: torch.Tensor     # int32 [n]: their destinations
+    total: torch.Tensor       # int64 [4]: R, resets
+    cls: torch.Tensor | None  # uint8 [n], arrival order: native.TCP_*
+    _bounds: np.ndarray | None = None
+    _totals: tuple | None = None
+
+    def bounds(self) -> np.ndarray:
+        """first on the host (synchronises once)."""
+        if self._bounds is None:
+            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        return self._bounds
+
+    def totals(self) -> tuple:
+        """(R, resets) on the host (synchronises once)."""
+        if self._totals is None:
+            t = self.total.cpu().numpy()
+            self._totals = (int(t[0]), int(t[1]))
+        return self._totals
+
+    def runs(self) -> tuple:
+        """(run_conn [R], run_first [R + 1]): run r is connection run_conn[r],
+        positions run_first[r] .. run_first[r + 1] of the grouped order."""
+        r = self.totals()[0]
+        return self.run_conn[:r], self.run_first[:r + 1]
+
+    def segs(self, conn_run: int) -> torch.Tensor:
+        """The records of run conn_run, a connection's segments in arrival order (a view)."""
+        r = self.totals()[0]
+        if not 0 <= int(conn_run) < r:
+            raise ValueError(f"conn_run: need 0..{r - 1}")
+        rf = self.run_first[int(conn_run):int(conn_run) + 2].cpu().numpy().view(np.uint32)
+        return self.seg[int(rf[0]):int(rf[1])]
+
+    @property
+    def resets(self) -> tuple:
+        """(l4, dst): the RST answers as an L4 batch of 20-byte segments and
+        their destinations, what ipv4_send takes with proto 6 (no SEND_L4)."""
+        k = self.totals()[1]
+        dev = self.rst.device
+        off = torch.arange(k, dtype=torch.int64, device=dev) * 20
+        length = torch.full((k,), 20, dtype=torch.int32, device=dev)
+        return (PacketBatch(data=self.rst, off=off, length=length, bytes_len=20 * k, max_len=20 if k else 0),
+                self.rst_dst[:k])
+
+    def taken(self, space: int) -> int:
+        """How many of the answers send_packet_without_tcb accepts with
+        `space` bytes of _queue_space: the list is stable, so they are the
+        first taken(space) of it (tcp.hh:946-953)."""
+        if int(space) < 0:
+            raise ValueError("space: need >= 0")
+        return min(self.totals()[1], int(space) // 20)
+
+
+def tcp_rx_check(b: PacketBatch, status, conns, host, need, reject, index=None, cls=None, flags=0) -> tuple:
+    """What tcp_rx refuses before any launch; returns (n, nbatch)."""
+    if not isinstance(b, PacketBatch):
+        raise ValueError("b: need a PacketBatch of IPv4 frames (an eth_rx bucket)")
+    nbatch = b.n
+    if nbatch > 0xFFFFFFFF:
+        raise ValueError("b: at most 2^32-1 frames")
+    if not isinstance(status, torch.Tensor) or status.dim() != 1:
+        raise ValueError("status: need the 1-D uint8 tensor the frames call wrote, one entry per frame")
+    _need(status, nbatch, torch.uint8, "status", b.device)
+    _udp_masks(host, need, reject)
+    if int(flags) & ~native.TCP_CSUM_OFFLOAD:
+        raise ValueError(f"flags: unknown bits in {int(flags):#x}")
+    n = nbatch
+    if index is not None:
+        if not isinstance(index, torch.Tensor) or index.dim() != 1:
+            raise ValueError("index: need a 1-D int32 tensor of batch frame indices")
+        n = int(index.numel())
+        if n > 0xFFFFFFFF:
+            raise ValueError("index: at most 2^32-1 entries")
+        _need(index, n, torch.int32, "index", b.device)
+    if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
+        raise ValueError("cls: need a 1-D uint8 tensor of one entry per frame")
+    _need(cls, n, torch.uint8, "cls", b.device)
+    if not isinstance(conns, TcpConns):
+        raise ValueError("conns: need a TcpConns")
+    if conns.device != b.device:
+        raise ValueError(f"conns: the table lives on {conns.device}, the data on {b.device}")
+    return n, nbatch
+
+
+def tcp_rx(b: PacketBatch, status: torch.Tensor, conns: TcpConns, host: int, need: int = TCP_NEED,
+           reject: int = TCP_REJECT, index: torch.Tensor | None = None, flags: int = 0, want_class: bool = True,
+           cls: torch.Tensor | None = None, stream=None) -> TcpRxResult:
+    """sccsum_tcp_rx: the stateless part of tcp::received (tcp.hh:865-942) for
+    the non-fragment frames of an IPv4 bucket — for us? TCP? the header and
+    its data_offset, the connid looked up, then the listening ports, then the
+    RST of respond_with_reset — ending in segments grouped per connection.
+
+        r = tcp_rx(ip, status, conns, me)              # index=: a shard's slice of Steer.run's order
+        run_conn, run_first = r.runs()
+        r.segs(k)                                      # run k's records, arrival order: one tcb's input
+        l4, dst = r.resets                             # -> ipv4_send(l4, dst, proto 6, ...) -> eth_send
+        r.taken(space)                                 # how many of them _queue_space accepts
+
+    flags=native.TCP_CSUM_OFFLOAD: the answers carry the folded pseudo-header
+    sum instead of the full checksum."""
+    lib = native.load()
+    n, nbatch = tcp_rx_check(b, status, conns, host, need, reject, index, cls, flags)
+    dev = b.device
+    if cls is None and want_class:
+        cls = _scratch(max(n, 1), dev, stream, torch.uint8)
+    k = max(n, 1)
+    runs = min(n, conns.nconns) + 1
+    first = _scratch(5, dev, stream, torch.int32)
+    order = _scratch(k, dev, stream, torch.int32)
+    seg = _scratch(4 * k, dev, stream, torch.int64)
+    src = _scratch(k, dev, stream, torch.int32)
+    run_conn = _scratch(runs, dev, stream, torch.int32)
+    run_first = _scratch(runs, dev, stream, torch.int32)
+    rst = _scratch(5 * k + 3, dev, stream, torch.int32)   # 20 n bytes, padded to 16 for the batch it becomes
+    rst_dst = _scratch(k, dev, stream, torch.int32)
+    total = _scratch(4, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_tcp_rx_workspace(n, conns.nconns)), dev, stream)
+    empty = nbatch == 0  # an empty tensor has no address
+    code = lib.sccsum_tcp_rx(
+        ctypes_ptr(b.data), b.bytes_len, None if empty else ctypes_ptr(b.off), None if empty else ctypes_ptr(b.length),
+        nbatch, None if empty else ctypes_ptr(status), int(need), int(reject), int(host), conns.handle,
+        None if index is None or n == 0 else ctypes_ptr(index), n, int(flags), _ptr(cls), ctypes_ptr(first),
+        ctypes_ptr(order), ctypes_ptr(seg), ctypes_ptr(src), ctypes_ptr(run_conn), ctypes_ptr(run_first),
+        ctypes_ptr(rst), ctypes_ptr(rst_dst), ctypes_ptr(total), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_tcp_rx")
+    return TcpRxResult(source=b, order=order[:n], first=first, seg=seg.view(torch.uint8).view(-1, 32)[:n],
+                       src_all=src[:n], run_conn=run_conn, run_first=run_first, rst=rst.view(torch.uint8),
+                       rst_dst=rst_dst[:n], total=total, cls=None if cls is None else cls[:n])
+
+
+@dataclass
+class TcpSendResult:
+    """What sccsum_tcp_send wrote (include/sccsum.h, "TCP layer"): the headers
+    lie in the payloads' headroom, in payloads.data itself."""
+    l4: PacketBatch            # header + payload per segment: what ipv4_send takes
+    sum_batch: PacketBatch     # the spans whose results (with seeds) are ipv4_send's l4sum
+    seeds: torch.Tensor        # int32 [n]
+    proto: torch.Tensor        # uint8 [n]: 6
+    needs_csum: torch.Tensor   # uint8 [n]: offload_info::needs_csum
+    tso_seg: torch.Tensor      # int16 [n]: offload_info::tso_seg_size
+    status: torch.Tensor       # uint8 [n]: native.ST_OK, or ST_RANGE / ST_MALFORMED (no header written)
+
+
+def tcp_send_check(payloads: PacketBatch, out, src_host, mtu, flags) -> int:
+    """What tcp_send refuses before any launch; returns n."""
+    if not isinstance(payloads, PacketBatch):
+        raise ValueError("payloads: need a PacketBatch of TCP payloads, each with hdr_len bytes of headroom")
+    dev, n = payloads.device, payloads.n
+    if n > 0xFFFFFFFF:
+        raise ValueError("payloads: at most 2^32-1 segments")
+    if not 68 <= int(mtu) <= 65535:
+        raise ValueError(f"mtu: need 68..65535, got {mtu}")
+    if int(flags) & ~(native.TCP_CSUM_OFFLOAD | native.TCP_TSO):
+        raise ValueError(f"flags: unknown bits in {int(flags):#x}")
+    if not 0 <= int(src_host) <= 0xFFFFFFFF:
+        raise ValueError("src_host: need a host-order IPv4 address, 0..2^32-1")
+    if not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[1] != 24:
+        raise ValueError("out: need a uint8 [n, 24] tensor of sccsum_tcp_out records (TCP_OUT_DTYPE)")
+    _need(out, 24 * n, torch.uint8, "out", dev)
+    return n
+
+
+def tcp_send(payloads: PacketBatch, out: torch.Tensor, src_host: int, mtu: int, flags: int = 0,
+             stream=None) -> TcpSendResult:
+    """sccsum_tcp_send: tcb::output_one's header (tcp.hh:1620-1698) into the
+    hdr_len bytes in front of every payload — the caller's headroom, whose
+    last hdr_len - 20 bytes already hold the options — and the checksum
+    pass's spans and seeds.
+
+        t = tcp_send(payloads, out, me, 1500)          # out: TCP_OUT_DTYPE records as uint8 [n, 24]
+        l4sum = spans(t.sum_batch, seeds=t.seeds)
+        r = ipv4_send(t.l4, dst, t.proto, 1500, me, ids=ids, l4sum=l4sum, flags=native.SEND_L4)
+        wire = eth_send(r, dst, table, hw, me, netmask, gw).pack()
+
+    With native.TCP_CSUM_OFFLOAD the field gets the folded pseudo-header sum
+    and needs_csum = 1; with native.TCP_TSO too a payload longer than its mss
+    gets a pseudo-header of length 0 and tso_seg = mss."""
+    lib = native.load()
+    n = tcp_send_check(payloads, out, src_host, mtu, flags)
+    dev = payloads.device
+    k = max(n, 1)
+    l4_off = _scratch(k, dev, stream, torch.int64)
+    l4_len = _scratch(k, dev, stream, torch.int32)
+    sum_len = _scratch(k, dev, stream, torch.int32)
+    seeds = _scratch(k, dev, stream, torch.int32)
+    tso = _scratch(k, dev, stream, torch.int16)
+    proto = _scratch(k, dev, stream, torch.uint8)
+    needs_csum = _scratch(k, dev, stream, torch.uint8)
+    status = _scratch(k, dev, stream, torch.uint8)
+    opts = native.TcpOpts(int(src_host), int(mtu), int(flags))
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_tcp_send(
+        ctypes.addressof(opts), ctypes_ptr(payloads.data), payloads.bytes_len,
+        None if empty else ctypes_ptr(payloads.off), None if empty else ctypes_ptr(payloads.length),
+        None if empty else ctypes_ptr(out), n, ctypes_ptr(l4_off), ctypes_ptr(l4_len), ctypes_ptr(sum_len),
+        ctypes_ptr(seeds), ctypes_ptr(tso), ctypes_ptr(proto), ctypes_ptr(needs_csum), ctypes_ptr(status),
+        _stream(stream))
+    native.check(code, "sccsum_tcp_send")
+    ml = payloads.max_len + 60 if payloads.max_len else 0
+    l4 = PacketBatch(data=payloads.data, off=l4_off[:n], length=l4_len[:n], bytes_len=payloads.bytes_len, max_len=ml)
+    sums = PacketBatch(data=payloads.data, off=l4_off[:n], length=sum_len[:n], bytes_len=payloads.bytes_len, max_len=ml)
+    return TcpSendResult(l4=l4, sum_batch=sums, seeds=seeds[:n], proto=proto[:n], needs_csum=needs_csum[:n],
+                         tso_seg=tso[:n], status=status[:n])
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

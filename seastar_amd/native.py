@@ -163,6 +163,19 @@ _PROTOS = {
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sccsum_udp_send": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),
+    "sccsum_tcp_conns_create": (ctypes.c_int, [ctypes.c_int, _vp, _u32, _vp, _u32, ctypes.POINTER(_vp)]),
+    "sccsum_tcp_conns_create_host": (ctypes.c_int, [_vp, _u32, _vp, _u32, ctypes.POINTER(_vp)]),
+    "sccsum_tcp_conns_destroy": (ctypes.c_int, [_vp]),
+    "sccsum_tcp_conns_lookup": (ctypes.c_int64, [_vp, _u32, _u32, ctypes.c_uint16, ctypes.c_uint16]),
+    "sccsum_tcp_conns_listening": (ctypes.c_int, [_vp, ctypes.c_uint16]),
+    "sccsum_tcp_conns_slot": (_u32, [_u32, _u32, ctypes.c_uint16, ctypes.c_uint16, _u32]),
+    "sccsum_tcp_conns_bits": (_u32, [_vp]),
+    "sccsum_tcp_conns_count": (_u32, [_vp]),
+    "sccsum_tcp_rx_workspace": (_u64, [_u64, _u32]),
+    "sccsum_tcp_rx": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _u32, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sccsum_tcp_send": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -273,6 +286,45 @@ UDP_QUEUE_SIZE = 1024  # ipv4_udp::default_queue_size
 
 class UdpOpts(ctypes.Structure):
     """sccsum_udp_opts: what ipv4_udp::send takes from its ipv4 (source address, MTU, offload flags)."""
+    _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+TCP_CONN = 0          # tcp_rx classes: a known connection, a listening port, answered with a RST
+TCP_LISTEN = 1
+TCP_RESET = 2
+TCP_NOCONN = 3        # ... and of dropped frames: a RST nobody owns, a bad header, not the TCP layer's
+TCP_SHORT = 0xFE
+TCP_SKIP = 0xFD
+TCP_MAX_CONNS = 1 << 20
+TCP_HDR = 20          # tcp_hdr::len
+TCP_CSUM_OFFLOAD = 0x01
+TCP_TSO = 0x02
+TCP_NO_CONN = 0xFFFFFFFF  # sccsum_tcp_seg.conn outside bucket 0
+
+
+class TcpConn(ctypes.Structure):
+    """sccsum_tcp_conn: one connid of the connection table (12 bytes, host order)."""
+    _fields_ = [("local_ip", ctypes.c_uint32), ("foreign_ip", ctypes.c_uint32), ("local_port", ctypes.c_uint16),
+                ("foreign_port", ctypes.c_uint16)]
+
+
+class TcpSeg(ctypes.Structure):
+    """sccsum_tcp_seg: one parsed segment of tcp_rx's grouped order (32 bytes)."""
+    _fields_ = [("pay_off", ctypes.c_uint64), ("pay_len", ctypes.c_uint32), ("seq", ctypes.c_uint32),
+                ("ack", ctypes.c_uint32), ("conn", ctypes.c_uint32), ("window", ctypes.c_uint16),
+                ("sport", ctypes.c_uint16), ("dport", ctypes.c_uint16), ("flags", ctypes.c_uint8),
+                ("hdr_len", ctypes.c_uint8)]
+
+
+class TcpOut(ctypes.Structure):
+    """sccsum_tcp_out: what output_one puts into one segment's header (24 bytes)."""
+    _fields_ = [("dst", ctypes.c_uint32), ("seq", ctypes.c_uint32), ("ack", ctypes.c_uint32),
+                ("sport", ctypes.c_uint16), ("dport", ctypes.c_uint16), ("window", ctypes.c_uint16),
+                ("flags", ctypes.c_uint8), ("hdr_len", ctypes.c_uint8), ("mss", ctypes.c_uint32)]
+
+
+class TcpOpts(ctypes.Structure):
+    """sccsum_tcp_opts: what output_one takes from its ipv4 (source address, MTU, offload flags)."""
     _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
