@@ -1581,6 +1581,122 @@ int sccsum_tcp_send(const sccsum_tcp_opts* opts, void* d_bytes, uint64_t bytes_l
                     uint32_t* d_l4_len, uint32_t* d_sum_len, uint32_t* d_seed, uint16_t* d_tso_seg, uint8_t* d_proto,
                     uint8_t* d_needs_csum, uint8_t* d_status, void* stream);
 
+/* ---- TCP receive fast path: the in-sequence data of every connection's run ------------
+ * Van Jacobson's header prediction for a batch.  Of tcb::input_handle_other_state
+ * (include/seastar/net/tcp.hh:1215-1575) almost every segment of a bulk receiver
+ * takes one path: acceptable (tcp.hh:1058-1076), exactly at RCV.NXT, with data,
+ * no control flag besides ACK (PSH allowed), acknowledging nothing new.  There the
+ * reference does only step 4.7 (tcp.hh:1497-1521): the text is appended to
+ * _rcv.data, _rcv.next advances, _rcv.window is recomputed (tcp.hh:424-427) and
+ * should_send_ack (tcp.hh:1845-1872) is stepped.  No send-side state moves, so
+ * segment i's outcome depends only on sums over the segments before it.
+ *
+ * sccsum_tcp_rx_data takes the leading stretch of such segments of every run of
+ * sccsum_tcp_rx's bucket 0 and leaves the host one record per run, plus the rest
+ * of any run that left the straight path: d_seg[d_run_first[r] + taken ..
+ * d_run_first[r + 1]), which the host walks with its real tcb as before, starting
+ * from the state in the run record.  Whatever the device does not take reaches
+ * the host whole and in order, so no outcome depends on the device.
+ *
+ * Inputs: d_seg, d_first, d_run_conn, d_run_first, d_total (here d_rx_total) as
+ * sccsum_tcp_rx left them on the device, and its n (an upper bound that sizes the
+ * launches; bucket 0 ends at d_first[1], R is d_rx_total[0]: no host
+ * synchronisation, capturable).  d_bytes is the frames' buffer and is never read:
+ * it only forms src = d_bytes + pay_off.  d_rcv[nconns], indexed by connection
+ * index, 16-byte aligned, is the host's view of each tcb:
+ *   next, window   _rcv.next, _rcv.window as it stands (tcp.hh:1059-1075)
+ *   room           max_receive_buf_size - data_size, 0 if data_size is larger (tcp.hh:425)
+ *   cap            get_default_receive_window_size() (tcp.hh:418-422)
+ *   snd_una, mss   _snd.unacknowledged, _rcv.mss
+ *   flags          SCCSUM_TCP_RCV_ELIGIBLE: set by the host only for a tcb in
+ *                  ESTABLISHED with an empty _rcv.out_of_order, _snd.window > 0 and
+ *                  _snd.unacknowledged <= _snd.next; _NR_FULL:
+ *                  _nr_full_seg_received (0 or 1); _ACK_ARMED: _delayed_ack.armed()
+ * room and cap above 2^30 are read as 2^30.
+ *
+ * The rule, per run r of connection c = d_run_conn[r], with a running next,
+ * window, room that start from d_rcv[c]: segment i is taken iff every earlier one
+ * was and none of these holds, tested in this order; the first that holds is the
+ * run's `stop`:
+ *   _STOP_INELIGIBLE  ELIGIBLE clear
+ *   _STOP_WINDOW      pay_len > 0 and window == 0          (tcp.hh:1072-1075)
+ *   _STOP_SEQ         seq != next                          (tcp.hh:1231-1245)
+ *   _STOP_FLAGS       (flags & 0x37) != 0x10: FIN, SYN, RST or URG, or no ACK
+ *   _STOP_ACK         ack != snd_una                       (tcp.hh:1336-1444)
+ *   _STOP_EMPTY       pay_len == 0: a pure ACK             (tcp.hh:1401)
+ *   _STOP_CAPACITY    below
+ *   _STOP_END (0)     the run is exhausted
+ * A taken segment: next += pay_len (mod 2^32); room = room >= pay_len ? room -
+ * pay_len : 0; window = min(room, cap); one step of should_send_ack(pay_len) with
+ * the connection's mss (its argument is a uint16_t: pay_len's low 16 bits), and
+ * when that returns true the closing clear_delayed_ack(); output() (tcp.hh:1570-
+ * 1574): the timer is off and _ACK_NOW is set.  Sums over a run are 64-bit: the
+ * comparison against room does not wrap.
+ *
+ * d_run[R] (room for min(n, nconns) + 1, 8-byte aligned): taken, bytes (their
+ * text); next, window, room after them (window as given when taken == 0);
+ * desc_first, the exclusive scan of taken, and dst_off, that of bytes; flags:
+ * _NR_FULL and _ACK_ARMED after them, _ACK_REARMED: arm(200 ms) was called during
+ * them (when _ACK_ARMED is set too, the deadline is now + 200 ms, else the timer
+ * the host holds is still the one that runs), _ACK_NOW: output() was called at
+ * least once; stop.
+ * d_desc[n] (8-byte aligned): taken segment k of run r is d_desc[desc_first + k] =
+ * {d_bytes + pay_off, its dst_off, pay_len}, grouped by run in arrival order: one
+ * sccsum_gather(d_desc, d_total[0], buf) packs every connection's new in-order
+ * bytes, run r's at [dst_off, dst_off + bytes).  Entries from d_total[0] on are
+ * not written.
+ * Capacity (sccsum_ipv4_send's prefix rule): runs are taken in run order while the
+ * packed text of runs 0..r is <= max_bytes (<= 2^32 - 1).  From the first run that
+ * does not fit onward taken = 0, stop = _STOP_CAPACITY and the state is as given.
+ * d_total[4] = {sum of taken as emitted, sum of bytes as emitted, the bytes needed
+ * without the capacity, 0}, 8-byte aligned.
+ *
+ * Plain dependent launches on `stream` (tile, carry, tile, carry, place, and one
+ * over the runs), no allocation, no memset, no atomic; two runs give identical
+ * bytes.  d_workspace: sccsum_tcp_rx_data_workspace(n, nconns) bytes, 16-byte
+ * aligned.  No output may overlap another array of the call.  SCCSUM_EINVAL
+ * before any device work: a NULL required pointer (d_total and the workspace
+ * always; with n != 0 every other one but d_bytes, and d_rcv unless nconns == 0),
+ * misalignment (d_rcv and the workspace 16; d_seg, d_desc, d_total, d_rx_total and
+ * d_run 8; the 32-bit arrays 4), n > 2^32 - 1, nconns > SCCSUM_TCP_MAX_CONNS,
+ * max_bytes > 2^32 - 1, a stream of another device than the current one.  n == 0
+ * writes d_total (all 0) and is SCCSUM_OK. */
+#define SCCSUM_TCP_RCV_ELIGIBLE    0x01u
+#define SCCSUM_TCP_RCV_NR_FULL     0x02u
+#define SCCSUM_TCP_RCV_ACK_ARMED   0x04u
+#define SCCSUM_TCP_RCV_ACK_REARMED 0x08u
+#define SCCSUM_TCP_RCV_ACK_NOW     0x10u
+#define SCCSUM_TCP_STOP_END        0u
+#define SCCSUM_TCP_STOP_INELIGIBLE 1u
+#define SCCSUM_TCP_STOP_WINDOW     2u
+#define SCCSUM_TCP_STOP_SEQ        3u
+#define SCCSUM_TCP_STOP_FLAGS      4u
+#define SCCSUM_TCP_STOP_ACK        5u
+#define SCCSUM_TCP_STOP_EMPTY      6u
+#define SCCSUM_TCP_STOP_CAPACITY   7u
+
+typedef struct sccsum_tcp_rcv {
+    uint32_t next, window, room, cap, snd_una;
+    uint16_t mss;
+    uint8_t flags; /* SCCSUM_TCP_RCV_ELIGIBLE | _NR_FULL | _ACK_ARMED */
+    uint8_t pad;
+    uint32_t reserved[2]; /* ignored */
+} sccsum_tcp_rcv;
+typedef struct sccsum_tcp_rcv_run {
+    uint32_t taken, bytes;
+    uint32_t next, window, room;
+    uint32_t desc_first, dst_off;
+    uint8_t flags; /* SCCSUM_TCP_RCV_NR_FULL | _ACK_ARMED | _ACK_REARMED | _ACK_NOW */
+    uint8_t stop;  /* SCCSUM_TCP_STOP_* */
+    uint16_t pad;
+} sccsum_tcp_rcv_run;
+
+uint64_t sccsum_tcp_rx_data_workspace(uint64_t n, uint32_t nconns);
+int sccsum_tcp_rx_data(const void* d_bytes, const sccsum_tcp_seg* d_seg, const uint32_t* d_first,
+                       const uint32_t* d_run_conn, const uint32_t* d_run_first, const uint64_t* d_rx_total, uint64_t n,
+                       const sccsum_tcp_rcv* d_rcv, uint32_t nconns, uint64_t max_bytes, sccsum_tcp_rcv_run* d_run,
+                       sccsum_gather_desc* d_desc, uint64_t* d_total, void* d_workspace, void* stream);
+
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);
 int sccsum_host_free(void* p);

@@ -932,6 +932,50 @@ public:
     }
 };
 
+// TCP rx, the data (<sccsum.h> sccsum_tcp_rx_data): header prediction for a
+// batch.  The leading stretch of every run of tcp_rx's bucket 0 that is
+// acceptable, exactly at RCV.NXT, carries text, no control flag besides ACK /
+// PSH and acknowledges nothing new — step 4.7 of input_handle_other_state
+// (tcp.hh:1497-1521) and nothing else — becomes one run record and one gather
+// descriptor per segment; the rest of a run is the tcb's to walk, from the
+// state in the record.  No byte moves.
+//   tcp_rx_data data(conns.count());
+//   data.run(ip.bytes, rx_out, n, d_rcv, max_bytes, out, d_ws, stream);   // rx_out: what tcp_rx::run wrote
+//   sccsum_gather(out.desc, total[0], d_stream_buf, stream);             // run r's bytes at [dst_off, + bytes)
+class tcp_rx_data {
+    uint32_t _nconns;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays; <sccsum.h>, "TCP receive fast path")
+    struct outputs {
+        sccsum_tcp_rcv_run* run = nullptr;   // min(n, nconns) + 1
+        sccsum_gather_desc* desc = nullptr;  // n
+        uint64_t* total = nullptr;           // 4: taken, bytes as emitted; the bytes needed
+    };
+
+    // nconns: the entries of d_rcv, the table's count()
+    explicit tcp_rx_data(uint32_t nconns) : _nconns(nconns) {}
+
+    uint32_t nconns() const noexcept { return _nconns; }
+
+    uint64_t workspace(uint64_t n) const noexcept { return sccsum_tcp_rx_data_workspace(n, _nconns); }
+
+    // d_bytes: the frames' buffer (never read); rx, n: tcp_rx::run's outputs as they stand on the device and
+    // its n; d_rcv: one sccsum_tcp_rcv per connection, 16-byte aligned; max_bytes <= 2^32 - 1
+    void run(const void* d_bytes, const tcp_rx::outputs& rx, uint64_t n, const sccsum_tcp_rcv* d_rcv,
+             uint64_t max_bytes, const outputs& out, void* d_workspace, void* stream) const {
+        check(sccsum_tcp_rx_data(d_bytes, rx.seg, rx.first, rx.run_conn, rx.run_first, rx.total, n, d_rcv, _nconns,
+                                 max_bytes, out.run, out.desc, out.total, d_workspace, stream),
+              "sccsum_tcp_rx_data");
+    }
+};
+
 // TCP tx (<sccsum.h> sccsum_tcp_send): tcb::output_one's header (tcp.hh:1620-1698)
 // written into the hdr_len bytes of headroom in front of every payload, the
 // caller's options behind it, and the spans and seeds of the checksum pass

@@ -1858,6 +1858,118 @@ def tcp_rx(b: PacketBatch, status: torch.Tensor, conns: TcpConns, host: int, nee
                        rst_dst=rst_dst[:n], total=total, cls=None if cls is None else cls[:n])
 
 
+TCP_RCV_DTYPE = np.dtype([("next", "<u4"), ("window", "<u4"), ("room", "<u4"), ("cap", "<u4"), ("snd_una", "<u4"),
+                          ("mss", "<u2"), ("flags", "u1"), ("pad", "u1"), ("reserved", "<u4", (2,))])
+TCP_RCV_RUN_DTYPE = np.dtype([("taken", "<u4"), ("bytes", "<u4"), ("next", "<u4"), ("window", "<u4"), ("room", "<u4"),
+                              ("desc_first", "<u4"), ("dst_off", "<u4"), ("flags", "u1"), ("stop", "u1"),
+                              ("pad", "<u2")])
+
+
+@dataclass
+class TcpRxDataResult:
+    """What sccsum_tcp_rx_data wrote (include/sccsum.h, "TCP receive fast
+    path"): the leading in-sequence stretch of every run of tcp_rx's bucket 0."""
+    rx: TcpRxResult
+    run: torch.Tensor          # uint8 [>= R, 32]: sccsum_tcp_rcv_run records (TCP_RCV_RUN_DTYPE on the host)
+    desc: torch.Tensor         # uint8 [16 n]: one sccsum_gather_desc per taken segment, grouped by run
+    total: torch.Tensor        # int64 [4]: taken, bytes as emitted; the bytes needed without max_bytes
+    _totals: tuple | None = None
+    _runs: np.ndarray | None = None
+
+    def totals(self) -> tuple:
+        """(taken, bytes, needed) on the host (synchronises once)."""
+        if self._totals is None:
+            t = self.total.cpu().numpy()
+            self._totals = (int(t[0]), int(t[1]), int(t[2]))
+        return self._totals
+
+    @property
+    def runs(self) -> torch.Tensor:
+        """The R run records (a view)."""
+        return self.run[:self.rx.totals()[0]]
+
+    def runs_host(self) -> np.ndarray:
+        """The run records on the host as TCP_RCV_RUN_DTYPE (synchronises once)."""
+        if self._runs is None:
+            self._runs = self.runs.cpu().numpy().reshape(-1).view(TCP_RCV_RUN_DTYPE)
+        return self._runs
+
+    @property
+    def descs(self) -> torch.Tensor:
+        """The descriptors of the taken segments, uint8 [taken, 16] (DESC_DTYPE on the host)."""
+        return self.desc.view(-1, 16)[:self.totals()[0]]
+
+    def pack(self, stream=None) -> torch.Tensor:
+        """Every connection's new in-order bytes packed back to back: run k's
+        lie at [dst_off, dst_off + bytes) of the returned uint8 buffer."""
+        taken, nbytes, _ = self.totals()
+        data = _scratch(_round16(nbytes) or 16, self.desc.device, stream)
+        if taken:
+            native.check(native.load().sccsum_gather(ctypes_ptr(self.desc), taken, ctypes_ptr(data), _stream(stream)),
+                         "sccsum_gather")
+        return data
+
+    def rest(self, conn_run: int) -> torch.Tensor:
+        """The records of run conn_run the host still has to walk with its
+        tcb, from the state in the run record: segs(conn_run)[taken:]."""
+        segs = self.rx.segs(conn_run)
+        return segs[int(self.runs_host()["taken"][int(conn_run)]):]
+
+
+def tcp_rx_data_check(rx, rcv, max_bytes) -> tuple:
+    """What tcp_rx_data refuses before any launch; returns (n, nconns)."""
+    if not isinstance(rx, TcpRxResult):
+        raise ValueError("rx: need the TcpRxResult of tcp_rx")
+    dev = rx.seg.device
+    n = int(rx.seg.shape[0])
+    if not isinstance(rcv, torch.Tensor) or rcv.dim() != 2 or rcv.shape[1] != 32:
+        raise ValueError("rcv: need a uint8 [nconns, 32] tensor of sccsum_tcp_rcv records (TCP_RCV_DTYPE)")
+    nconns = int(rcv.shape[0])
+    if nconns > native.TCP_MAX_CONNS:
+        raise ValueError("rcv: at most 2^20 connections")
+    _need(rcv, 32 * nconns, torch.uint8, "rcv", dev)
+    if nconns and rcv.data_ptr() % 16:
+        raise ValueError("rcv: need a 16-byte aligned tensor")
+    if int(rx.run_conn.numel()) < min(n, nconns) + 1:
+        raise ValueError(f"rcv: {nconns} connections, but rx was made with a table of fewer")
+    if not 0 <= int(max_bytes) <= 0xFFFFFFFF:
+        raise ValueError("max_bytes: need 0..2^32-1")
+    return n, nconns
+
+
+def tcp_rx_data(rx: TcpRxResult, rcv: torch.Tensor, max_bytes: int = 0xFFFFFFFF, stream=None) -> TcpRxDataResult:
+    """sccsum_tcp_rx_data: header prediction for a batch — the leading stretch
+    of every connection's run that is acceptable, exactly at RCV.NXT, carries
+    data, no control flag besides ACK / PSH and acknowledges nothing new: step
+    4.7 of tcb::input_handle_other_state (tcp.hh:1497-1521) and nothing else.
+
+        d = tcp_rx_data(r, rcv)                        # rcv: TCP_RCV_DTYPE records as uint8 [nconns, 32]
+        buf = d.pack()                                 # the new in-order bytes of every connection
+        for k, run in enumerate(d.runs_host()):        # one record per connection: next, window, room, the ACK
+            ...                                        # buf[run.dst_off : run.dst_off + run.bytes] -> _rcv.data
+            d.rest(k)                                  # what the tcb still walks itself, from that state
+
+    Runs are taken while their packed text fits max_bytes; the runs from the
+    first that does not fit onward take nothing (stop = TCP_STOP_CAPACITY)."""
+    lib = native.load()
+    n, nconns = tcp_rx_data_check(rx, rcv, max_bytes)
+    dev = rx.seg.device
+    k = max(n, 1)
+    run = _scratch(4 * (min(n, nconns) + 1), dev, stream, torch.int64)
+    desc = _scratch(2 * k, dev, stream, torch.int64)
+    total = _scratch(4, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_tcp_rx_data_workspace(n, nconns)), dev, stream)
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_tcp_rx_data(
+        ctypes_ptr(rx.source.data), None if empty else ctypes_ptr(rx.seg), ctypes_ptr(rx.first),
+        ctypes_ptr(rx.run_conn), ctypes_ptr(rx.run_first), ctypes_ptr(rx.total), n,
+        ctypes_ptr(rcv) if nconns else None, nconns, int(max_bytes), ctypes_ptr(run), ctypes_ptr(desc),
+        ctypes_ptr(total), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_tcp_rx_data")
+    return TcpRxDataResult(rx=rx, run=run.view(torch.uint8).view(-1, 32), desc=desc.view(torch.uint8)[:16 * n],
+                           total=total)
+
+
 @dataclass
 class TcpSendResult:
     """What sccsum_tcp_send wrote (include/sccsum.h, "TCP layer"): the headers

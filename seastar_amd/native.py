@@ -176,6 +176,9 @@ _PROTOS = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sccsum_tcp_send": (ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp]),
+    "sccsum_tcp_rx_data_workspace": (_u64, [_u64, _u32]),
+    "sccsum_tcp_rx_data": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _u64, _vp, _vp, _vp, _vp,
+                                          _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -300,6 +303,19 @@ TCP_HDR = 20          # tcp_hdr::len
 TCP_CSUM_OFFLOAD = 0x01
 TCP_TSO = 0x02
 TCP_NO_CONN = 0xFFFFFFFF  # sccsum_tcp_seg.conn outside bucket 0
+TCP_RCV_ELIGIBLE = 0x01     # sccsum_tcp_rcv.flags: the tcb may take the straight path
+TCP_RCV_NR_FULL = 0x02      # ... and sccsum_tcp_rcv_run.flags: _nr_full_seg_received
+TCP_RCV_ACK_ARMED = 0x04    # _delayed_ack.armed()
+TCP_RCV_ACK_REARMED = 0x08  # run records only: arm(200 ms) was called during the stretch
+TCP_RCV_ACK_NOW = 0x10      # run records only: output() was called at least once
+TCP_STOP_END = 0            # sccsum_tcp_rcv_run.stop: why segment `taken` was not taken
+TCP_STOP_INELIGIBLE = 1
+TCP_STOP_WINDOW = 2
+TCP_STOP_SEQ = 3
+TCP_STOP_FLAGS = 4
+TCP_STOP_ACK = 5
+TCP_STOP_EMPTY = 6
+TCP_STOP_CAPACITY = 7
 
 
 class TcpConn(ctypes.Structure):
