@@ -15,11 +15,11 @@
 // depend on their order):
 //   eth_rx         eth_rx_count_kernel    class of every frame (-> d_class), the
 //                                         tile's per-bucket counts -> workspace
-//                  eth_rx_scan_kernel     ONE block: per bucket an exclusive scan
-//                                         over the tiles, the bases -> d_first
-//                  eth_rx_scatter_kernel  classes recomputed, rank inside the tile
-//                                         from wave match masks, the grouped arrays
-//   learn records  learn_tile / learn_carry / learn_place: a stable compaction
+//                  bucket_pass's scan     ONE block (scan_kernel): per bucket an exclusive
+//                                         scan over the tiles, the bases -> d_first
+//                  eth_rx_scatter_kernel  classes recomputed, offset inside the tile
+//                                         (bucket_pass's TileRank), the grouped arrays
+//   learn records  compact.h's tile / carry / place kernels over Candidate
 //   eth_send       eth_send_count_kernel  per datagram: resolved?, frames, layout
 //                                         bytes, descriptors; the tile's totals
 //                  eth_send_scan_kernel   ONE block: exclusive scan over the tiles,
@@ -37,20 +37,23 @@
 #include <vector>
 
 #include "bucket_pass.h"
+#include "compact.h"
 #include "host_launch.h"
 #include "sccsum.h"
 #include "wave_scan.h"
+#include "wire.h"
 
 namespace eth {
 
-using bucket_pass::lanes_below;
-using bucket_pass::match_bucket;
-using bucket_pass::scan_row;
+using bucket_pass::pitch_of;
 using host_launch::launch_kernel;
 using host_launch::misaligned;
+using host_launch::stream_ok;
 using wave_scan::block_inclusive_scan;
-using wave_scan::lane_id;
-using wave_scan::wave_inclusive_scan;
+using wire::fmix32;
+using wire::kIpHdrMin;
+using wire::kMaxDevices;
+using wire::tiles_of;
 
 constexpr int kWave = 64;
 constexpr int kBlock = 1024;                 // threads of every tile kernel: one frame / datagram each
@@ -59,29 +62,16 @@ constexpr uint32_t kTile = kBlock;
 constexpr uint32_t kMaxProtos = SCCSUM_ETH_MAX_PROTOS;
 constexpr uint32_t kMaxBuckets = kMaxProtos + 1;  // the registered protocols + the drop bucket
 constexpr uint32_t kEthHdr = 14;             // sizeof(eth_hdr): dst_mac, src_mac, eth_proto
-constexpr uint32_t kIpHdrMin = 20;
 constexpr int kEmitBlock = 256;
 constexpr uint32_t kEmitMaxBlocks = 16384;   // the emit grid strides over the frames past this
 constexpr uint32_t kMinBits = 4;             // at least 16 slots
 constexpr uint64_t kMacMask = 0xFFFFFFFFFFFFull;
 constexpr uint64_t kNoCut = ~uint64_t(0);
-constexpr int kMaxDevices = 64;
 constexpr int kHostOnly = -1;                // device of a table that has no device copy
 // eth_send workspace: [0] frames emitted, [1] datagrams taken (the prefix), then per tile
 // {frames, bytes, descriptors, unresolved} (totals, then their exclusive scan)
 constexpr uint64_t kWsHead = 4;
 constexpr int kQ = 4;
-
-__host__ __device__ inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
-
-__host__ __device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
 
 // Home slot of a key in a table of 2^bits slots (bits <= 31).
 __host__ __device__ inline uint32_t home_slot(uint32_t ip, uint32_t bits) {
@@ -157,38 +147,16 @@ __device__ __forceinline__ uint32_t classify(const Frames& F, const Protos& P, u
 __global__ __launch_bounds__(kBlock) void eth_rx_count_kernel(Frames F, Protos P, uint8_t* __restrict__ d_class,
                                                               uint32_t* __restrict__ ws, uint32_t pitch) {
     __shared__ uint32_t hist[kMaxBuckets];
-    if (threadIdx.x < kMaxBuckets) hist[threadIdx.x] = 0;
+    bucket_pass::hist_clear(hist);
     __syncthreads();
     const uint64_t i = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = i < F.n;
     const uint32_t c = valid ? classify(F, P, F.off[i], F.len[i]) : SCCSUM_ETH_UNKNOWN;
     const uint32_t b = c < P.k ? c : P.k;
-    const uint64_t m = match_bucket(b, valid);
-    // one LDS add per distinct bucket of the wave: only a count comes out
-    if (valid && (m & lanes_below()) == 0) atomicAdd(&hist[b], static_cast<uint32_t>(__popcll(m)));
+    bucket_pass::hist_add(hist, b, valid);
     if (valid && d_class) d_class[i] = static_cast<uint8_t>(c);
     __syncthreads();
-    if (threadIdx.x <= P.k) ws[uint64_t(threadIdx.x) * pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-// ONE block: wave b scans bucket b's row of per-tile counts in place, then
-// wave 0 scans the bucket totals into d_first (buckets + 1 entries).
-__global__ __launch_bounds__(kBlock) void eth_rx_scan_kernel(uint32_t* __restrict__ ws, uint32_t ntiles, uint32_t pitch,
-                                                             uint32_t buckets, uint32_t* __restrict__ d_first) {
-    __shared__ uint32_t total[kMaxBuckets];
-    const uint32_t wave = threadIdx.x / kWave;
-    if (wave < buckets) {
-        const uint32_t sum = scan_row(ws, wave, ntiles, pitch);
-        if (lane_id() == 0) total[wave] = sum;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const uint32_t lane = lane_id();
-        const uint32_t c = lane < buckets ? total[lane] : 0u;
-        const uint32_t incl = wave_inclusive_scan(c);
-        if (lane < buckets) d_first[lane] = incl - c;
-        if (lane == buckets - 1) d_first[buckets] = incl;
-    }
+    bucket_pass::hist_store(hist, P.k + 1u, ws, pitch);
 }
 
 __global__ __launch_bounds__(kBlock) void eth_rx_scatter_kernel(Frames F, Protos P, const uint32_t* __restrict__ ws,
@@ -197,13 +165,11 @@ __global__ __launch_bounds__(kBlock) void eth_rx_scatter_kernel(Frames F, Protos
                                                                 uint64_t* __restrict__ d_l3_off,
                                                                 uint32_t* __restrict__ d_l3_len,
                                                                 uint64_t* __restrict__ d_src_mac) {
-    // cnt[wave][bucket]: frames of the bucket in the wave, then their offset inside the tile;
     // base[bucket]: where the tile's frames of the bucket start in the grouped arrays
-    __shared__ uint32_t cnt[kWaves][kMaxBuckets];
     __shared__ uint32_t base[kMaxBuckets];
-    const uint32_t wave = threadIdx.x / kWave;
-    if (threadIdx.x < kWaves * kMaxBuckets) (&cnt[0][0])[threadIdx.x] = 0;
-    if (threadIdx.x <= P.k) base[threadIdx.x] = d_first[threadIdx.x] + ws[uint64_t(threadIdx.x) * pitch + blockIdx.x];
+    bucket_pass::TileRank<kWaves, 1, kMaxBuckets> rank;
+    rank.clear(P.k + 1u);
+    bucket_pass::bucket_base(base, P.k + 1u, d_first, ws, pitch);
     __syncthreads();
     const uint64_t i = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = i < F.n;
@@ -211,22 +177,12 @@ __global__ __launch_bounds__(kBlock) void eth_rx_scatter_kernel(Frames F, Protos
     const uint32_t len = valid ? F.len[i] : 0;
     const uint32_t c = valid ? classify(F, P, off, len) : SCCSUM_ETH_UNKNOWN;
     const uint32_t b = c < P.k ? c : P.k;
-    const uint64_t m = match_bucket(b, valid);
-    const uint32_t rank = static_cast<uint32_t>(__popcll(m & lanes_below()));
-    if (valid && rank == 0) cnt[wave][b] = static_cast<uint32_t>(__popcll(m));
+    rank.mark(0, b, valid);
     __syncthreads();
-    if (threadIdx.x <= P.k) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const uint32_t k = cnt[w][threadIdx.x];
-            cnt[w][threadIdx.x] = run;
-            run += k;
-        }
-    }
+    rank.scan(P.k + 1u);
     __syncthreads();
     if (!valid) return;
-    const uint64_t pos = uint64_t(base[b]) + cnt[wave][b] + rank;
+    const uint64_t pos = uint64_t(base[b]) + rank.offset(0, b);
     if (pos >= F.n) return;  // never for consistent inputs
     const bool classified = b < P.k;
     uint64_t mac = 0;
@@ -243,74 +199,43 @@ __global__ __launch_bounds__(kBlock) void eth_rx_scatter_kernel(Frames F, Protos
 
 // ---------------------------------------------------------------- learn records
 
-struct Learn {
+// compact.h's predicate: frame i's record when it is a learn candidate.  The
+// caller's status masks, the range and length tests again before the header
+// is read, the subnet test of ip.cc:147, then the table.
+struct Candidate {
     Frames F;
     const uint8_t* status;
     const uint64_t* mac;
     uint32_t need, reject, host, netmask;
     Table T;
+
+    struct Record {
+        uint64_t w[2];  // sccsum_arp_rec as two 64-bit words
+    };
+    using Out = sccsum_arp_rec;
+
+    __device__ __forceinline__ bool operator()(uint64_t i, Record* rec) const {
+        if (i >= F.n) return false;
+        if (!wire::status_passes(status[i], need, reject)) return false;
+        const uint64_t off = F.off[i];
+        const uint32_t len = F.len[i];
+        if (!in_buffer(F, off, len) || len < kIpHdrMin) return false;
+        const uint32_t src = wire::be32_at(F.bytes + off + 12);  // ip_hdr::src_ip
+        if (((src ^ host) & netmask) != 0 || src == host) return false;
+        const uint64_t m = mac[i];
+        uint64_t known = 0;
+        if (table_lookup(T, src, &known) && known == m) return false;
+        rec->w[0] = uint64_t(src) | (uint64_t(static_cast<uint32_t>(i)) << 32);
+        rec->w[1] = m;
+        return true;
+    }
+
+    static __device__ __forceinline__ void store(Out* __restrict__ d_rec, uint64_t pos, const Record& rec) {
+        uint64_t* const w = reinterpret_cast<uint64_t*>(d_rec + pos);
+        w[0] = rec.w[0];
+        w[1] = rec.w[1];
+    }
 };
-
-// Frame i's record when it is a learn candidate: the caller's status masks,
-// the range and length tests again before the header is read, the subnet
-// test of ip.cc:147, then the table.
-__device__ __forceinline__ bool candidate(const Learn& L, uint64_t i, uint64_t (&rec)[2]) {
-    if (i >= L.F.n) return false;
-    const uint32_t st = L.status[i];
-    if ((st & L.need) != L.need || (st & L.reject) != 0) return false;
-    const uint64_t off = L.F.off[i];
-    const uint32_t len = L.F.len[i];
-    if (!in_buffer(L.F, off, len) || len < kIpHdrMin) return false;
-    const uint8_t* const h = L.F.bytes + off + 12;  // ip_hdr::src_ip
-    const uint32_t src = (uint32_t(h[0]) << 24) | (uint32_t(h[1]) << 16) | (uint32_t(h[2]) << 8) | h[3];
-    if (((src ^ L.host) & L.netmask) != 0 || src == L.host) return false;
-    const uint64_t mac = L.mac[i];
-    uint64_t known = 0;
-    if (table_lookup(L.T, src, &known) && known == mac) return false;
-    rec[0] = uint64_t(src) | (uint64_t(static_cast<uint32_t>(i)) << 32);
-    rec[1] = mac;
-    return true;
-}
-
-__global__ __launch_bounds__(kBlock) void learn_tile_kernel(Learn L, uint32_t* __restrict__ tcount) {
-    __shared__ uint32_t part[kWaves];
-    uint64_t rec[2];
-    const uint32_t a = candidate(L, uint64_t(blockIdx.x) * kTile + threadIdx.x, rec) ? 1u : 0u;
-    uint32_t total;
-    (void)block_inclusive_scan<kWaves>(a, part, &total);
-    if (threadIdx.x == 0) tcount[blockIdx.x] = total;
-}
-
-// ONE block: the per-tile sums become inclusive prefixes in place; *d_count = the sum.
-__global__ __launch_bounds__(kBlock) void learn_carry_kernel(uint32_t* __restrict__ tcount, uint64_t ntiles,
-                                                             uint32_t* __restrict__ d_count) {
-    __shared__ uint32_t part[kWaves];
-    uint32_t carry = 0;
-    for (uint64_t base = 0; base < ntiles; base += kBlock) {
-        const uint64_t t = base + threadIdx.x;
-        const uint32_t v = t < ntiles ? tcount[t] : 0u;
-        uint32_t total;
-        const uint32_t incl = carry + block_inclusive_scan<kWaves>(v, part, &total);
-        if (t < ntiles) tcount[t] = incl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *d_count = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void learn_place_kernel(Learn L, const uint32_t* __restrict__ tcount,
-                                                             sccsum_arp_rec* __restrict__ d_rec) {
-    __shared__ uint32_t part[kWaves];
-    uint64_t rec[2];
-    const bool ok = candidate(L, uint64_t(blockIdx.x) * kTile + threadIdx.x, rec);
-    uint32_t total;
-    const uint32_t incl = block_inclusive_scan<kWaves>(ok ? 1u : 0u, part, &total);
-    const uint32_t base = blockIdx.x ? tcount[blockIdx.x - 1] : 0u;
-    if (ok) {
-        uint64_t* const w = reinterpret_cast<uint64_t*>(d_rec + (uint64_t(base) + incl - 1u));
-        w[0] = rec[0];
-        w[1] = rec[1];
-    }
-}
 
 // ---------------------------------------------------------------- eth_send
 
@@ -526,15 +451,6 @@ __global__ __launch_bounds__(kEmitBlock) void eth_send_emit_kernel(Send S, const
 
 // ---------------------------------------------------------------- host side
 
-// The launches run on the stream's device, which must be `want` (a table's
-// device), or with want < 0 the calling thread's current one, where the data is.
-int stream_ok(hipStream_t st, int want) {
-    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
-    const hipError_t e = host_launch::stream_devices(st, &dev, &sd);
-    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
-    return sd != (want < 0 ? dev : want) ? SCCSUM_EINVAL : SCCSUM_OK;
-}
-
 uint32_t bits_for(uint32_t n) {
     uint32_t bits = kMinBits;
     while ((uint64_t(1) << bits) < 2 * uint64_t(n)) ++bits;
@@ -658,7 +574,7 @@ int sccsum_arp_table_lookup(const sccsum_arp_table* t, uint32_t ip, uint64_t* ma
 }
 
 uint64_t sccsum_eth_rx_workspace(uint64_t n) {
-    const uint64_t pitch = (eth::tiles_of(n) + 3) & ~uint64_t(3);
+    const uint64_t pitch = eth::pitch_of(eth::tiles_of(n, eth::kTile));
     return eth::kMaxBuckets * pitch * 4u + 16u;  // the per-tile counts [9][pitch]
 }
 
@@ -690,22 +606,26 @@ int sccsum_eth_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off
     if (rc != SCCSUM_OK) return rc;
 
     const Frames F{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, n};
-    const uint32_t ntiles = static_cast<uint32_t>(tiles_of(n));
-    const uint32_t pitch = (ntiles + 3u) & ~3u;
+    const uint32_t ntiles = static_cast<uint32_t>(tiles_of(n, kTile));
+    const uint32_t pitch = pitch_of(ntiles);
     uint32_t* const ws = static_cast<uint32_t*>(d_workspace);
     hipError_t e = hipSuccess;
     if (ntiles) {
         e = launch_kernel(eth_rx_count_kernel, dim3(ntiles), dim3(kBlock), 0, st, F, P, d_class, ws, pitch);
         if (e != hipSuccess) return static_cast<int>(e);
     }
-    e = launch_kernel(eth_rx_scan_kernel, dim3(1), dim3(kBlock), 0, st, ws, ntiles, pitch, nprotos + 1u, d_first);
+    // at most nine buckets: always the one-block scan, which leaves no totals behind the rows
+    static_assert(kMaxBuckets <= bucket_pass::kScanOneBlockMax, "sccsum_eth_rx_workspace has no room for totals");
+    e = bucket_pass::scan_buckets<kBlock, kMaxBuckets>(st, ws, ntiles, pitch, nprotos + 1u, d_first, nullptr);
     if (e != hipSuccess || !ntiles) return static_cast<int>(e);
     e = launch_kernel(eth_rx_scatter_kernel, dim3(ntiles), dim3(kBlock), 0, st, F, P, static_cast<const uint32_t*>(ws),
                       pitch, static_cast<const uint32_t*>(d_first), d_order, d_l3_off, d_l3_len, d_src_mac);
     return static_cast<int>(e);
 }
 
-uint64_t sccsum_arp_learn_workspace(uint64_t n) { return (eth::tiles_of(n) * 4u + 15u + 16u) & ~uint64_t(15); }
+uint64_t sccsum_arp_learn_workspace(uint64_t n) {
+    return (eth::tiles_of(n, eth::kTile) * 4u + 15u + 16u) & ~uint64_t(15);
+}
 
 int sccsum_arp_learn_records(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
                              const uint8_t* d_status, uint32_t need, uint32_t reject, const uint64_t* d_src_mac,
@@ -725,24 +645,14 @@ int sccsum_arp_learn_records(const void* d_bytes, uint64_t bytes_len, const uint
     const int rc = stream_ok(st, table ? table->device : -1);
     if (rc != SCCSUM_OK) return rc;
 
-    const Learn L{Frames{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, n}, d_status, d_src_mac,
-                  need, reject, host, netmask, view(table)};
-    const uint64_t ntiles = tiles_of(n);
-    uint32_t* const tcount = static_cast<uint32_t*>(d_workspace);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(learn_tile_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, st, L, tcount);
-        if (e != hipSuccess) return static_cast<int>(e);
-    }
-    e = launch_kernel(learn_carry_kernel, dim3(1), dim3(kBlock), 0, st, tcount, ntiles, d_count);
-    if (e != hipSuccess || !ntiles) return static_cast<int>(e);
-    e = launch_kernel(learn_place_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, st, L,
-                      static_cast<const uint32_t*>(tcount), d_rec);
-    return static_cast<int>(e);
+    const Candidate C{Frames{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, n}, d_status, d_src_mac,
+                      need, reject, host, netmask, view(table)};
+    return static_cast<int>(
+        compact::run<kBlock>(st, C, tiles_of(n, kTile), static_cast<uint32_t*>(d_workspace), d_count, d_rec));
 }
 
 uint64_t sccsum_eth_send_workspace(uint64_t n) {
-    return ((eth::kWsHead + eth::kQ * eth::tiles_of(n)) * 8u + 15u) & ~uint64_t(15);
+    return ((eth::kWsHead + eth::kQ * eth::tiles_of(n, eth::kTile)) * 8u + 15u) & ~uint64_t(15);
 }
 
 int sccsum_eth_send(const sccsum_eth_opts* opts, const sccsum_arp_table* table, const uint32_t* d_dst,
@@ -784,7 +694,7 @@ int sccsum_eth_send(const sccsum_eth_opts* opts, const sccsum_arp_table* table, 
     const Send S{d_dst, d_dgram_first, n, d_desc, d_first, d_off, d_len, nframes, opts->host, opts->netmask,
                  opts->gw, view(table)};
     const SendOut O{d_eth, d_desc_out, d_first_out, d_off_out, d_len_out, d_frame_src, d_status, d_unresolved};
-    const uint64_t ntiles = tiles_of(n);
+    const uint64_t ntiles = tiles_of(n, kTile);
     uint64_t* const ws = static_cast<uint64_t*>(d_workspace);
     hipError_t e = hipSuccess;
     if (ntiles) {

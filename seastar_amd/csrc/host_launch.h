@@ -11,6 +11,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "sccsum.h"
+
 namespace host_launch {
 
 // p is not a multiple of a (a power of two); a null pointer is aligned.
@@ -30,6 +32,16 @@ inline hipError_t stream_devices(hipStream_t s, int* cur, int* sdev) {
     if (s != nullptr && (e = hipStreamGetDevice(s, &sd)) != hipSuccess) return e;
     *sdev = sd;
     return hipSuccess;
+}
+
+// The rx / tx layers' rule: the launches run on the stream's device, which must
+// be `want` (a table's device), or with want < 0 the calling thread's current
+// one, where the data is.
+inline int stream_ok(hipStream_t s, int want) {
+    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
+    const hipError_t e = stream_devices(s, &dev, &sd);
+    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
+    return sd != (want < 0 ? dev : want) ? SCCSUM_EINVAL : SCCSUM_OK;
 }
 
 // Every launch goes through hipLaunchKernel, which returns THIS launch's

@@ -18,9 +18,9 @@
 // Plain dependent launches on the caller's stream, no block ever waiting on
 // another one and no atomic deciding a position (the only atomics are LDS adds
 // into a histogram and LDS minima, whose results do not depend on their order):
-//   records:  rec_tile / rec_carry / rec_place   stable compaction of the accepted frames
+//   records:  compact.h's tile / carry / place over FrameRecord   stable compaction of the accepted frames
 //   reasm:    key                 (mix32(key) << 13 | offset / 8) per record
-//             6 x sort_count / sort_scan / sort_scatter   stable LSD radix sort, 8-bit digits
+//             6 x sort_count / bucket_pass's scan_rows / sort_scatter   stable LSD radix sort, 8-bit digits
 //             detect              head / tail of a group (equal mix), neighbour tests
 //             seg_tile / seg_carry / seg_place   segmented scan over the sorted order:
 //                                 a group's flags, its latest arrival, its head
@@ -35,28 +35,31 @@
 #include <cstdint>
 
 #include "bucket_pass.h"
+#include "compact.h"
 #include "host_launch.h"
 #include "sccsum.h"
 #include "sccsum_diag.h"
 #include "wave_scan.h"
+#include "wire.h"
 
 namespace reasm {
 
-using bucket_pass::lanes_below;
-using bucket_pass::match_bucket;
-using bucket_pass::scan_row;
+using bucket_pass::kDigits;
+using bucket_pass::scan_rows_kernel;
 using host_launch::launch_kernel;
 using host_launch::misaligned;
+using host_launch::stream_ok;
 using wave_scan::block_inclusive_scan;
-using wave_scan::lane_id;
+using wire::be32_at;
+using wire::fmix32;
+using wire::pseudo_seed;
+using wire::tiles_of;
 
 constexpr int kWave = 64;
 constexpr int kSortBlock = 256;            // threads of the sort's count / scatter kernels
 constexpr int kSortWaves = kSortBlock / kWave;
 constexpr int kSortRounds = 8;              // records per thread: round r of a tile is its records [256 r, 256 r + 256)
 constexpr uint32_t kSortTile = kSortBlock * kSortRounds;
-constexpr int kSlots = kSortRounds * kSortWaves;
-constexpr int kDigits = 256;
 constexpr int kScanBlock = 1024;            // threads of the scan kernels: one record each
 constexpr int kScanWaves = kScanBlock / kWave;
 constexpr uint32_t kScanTile = kScanBlock;
@@ -75,15 +78,6 @@ constexpr uint32_t kMixed = 4u;   // its key differs from its predecessor's: two
 constexpr uint32_t kBad = 8u;     // not plain: empty, overlaps its predecessor, or follows an MF-clear record
 constexpr uint32_t kGap = 16u;    // does not touch its predecessor / a head not at offset 0
 constexpr uint32_t kOpen = 32u;   // a tail with MF set: the last fragment is missing
-
-__host__ __device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
 
 // The 32-bit mix of an ipv4_frag_id the sort groups by.  For one (src, dst)
 // pair it is a bijection of (id, proto); distinct keys that collide differ in
@@ -122,11 +116,13 @@ __device__ __forceinline__ void store_rec(sccsum_frag_rec* __restrict__ rec, uin
     w[3] = r.w3;
 }
 
-__host__ __device__ inline uint64_t tiles_of(uint64_t n, uint32_t tile) { return (n + tile - 1) / tile; }
-
 // ---------------------------------------------------------------- records
 
-struct Frames {
+// compact.h's predicate: frame i's record when it is accepted.  The caller's
+// status masks, then the tests of ip.cc:128-144 again on the header itself (a
+// frame the masks let through is still never read outside the buffer), then
+// the destination (ip.cc:159-162).
+struct FrameRecord {
     const uint8_t* bytes;
     uint64_t bytes_len;
     const uint64_t* off;
@@ -134,76 +130,34 @@ struct Frames {
     const uint8_t* status;
     uint64_t n;
     uint32_t need, reject, host, tag;
-};
 
-__device__ __forceinline__ uint32_t be16_at(const uint8_t* p) { return (uint32_t(p[0]) << 8) | p[1]; }
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
-    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3];
-}
+    using Record = Rec;
+    using Out = sccsum_frag_rec;
 
-// Frame i's record when it is accepted: the caller's status masks, then the
-// tests of ip.cc:128-144 again on the header itself (a frame the masks let
-// through is still never read outside the buffer), then the destination
-// (ip.cc:159-162).
-__device__ __forceinline__ bool frame_record(const Frames& F, uint64_t i, Rec* out) {
-    if (i >= F.n) return false;
-    const uint32_t st = F.status[i];
-    if ((st & F.need) != F.need || (st & F.reject) != 0) return false;
-    const uint64_t off = F.off[i];
-    const uint32_t len = F.len[i];
-    if (off > F.bytes_len || len > F.bytes_len - off || len < 20) return false;
-    const uint8_t* const h = F.bytes + off;
-    const uint32_t hdr_len = 4u * (h[0] & 0xFu);
-    const uint32_t ip_len = be16_at(h + 2);
-    const uint32_t frag = be16_at(h + 6);
-    const uint32_t offset = (frag & 0x1FFFu) << 3;
-    if (len < ip_len || hdr_len > ip_len || offset + ip_len > 65535u) return false;
-    const uint32_t dst = be32_at(h + 16);
-    if (F.host != 0 && dst != F.host) return false;
-    out->frame = reinterpret_cast<uint64_t>(h);
-    out->addr = uint64_t(be32_at(h + 12)) | (uint64_t(dst) << 32);
-    out->w2 = uint64_t(be16_at(h + 4)) | (uint64_t(h[9]) << 16) | (uint64_t((frag >> 13) & 1u) << 24) |
-              (uint64_t(offset) << 32) | (uint64_t(hdr_len) << 48);
-    out->w3 = uint64_t(ip_len - hdr_len) | (uint64_t(F.tag) << 32);
-    return true;
-}
-
-__global__ __launch_bounds__(kScanBlock) void rec_tile_kernel(Frames F, uint32_t* __restrict__ tcount) {
-    __shared__ uint32_t part[kScanWaves];
-    Rec r;
-    const uint32_t a = frame_record(F, uint64_t(blockIdx.x) * kScanTile + threadIdx.x, &r) ? 1u : 0u;
-    uint32_t total;
-    (void)block_inclusive_scan<kScanWaves>(a, part, &total);
-    if (threadIdx.x == 0) tcount[blockIdx.x] = total;
-}
-
-// ONE block: the per-tile sums become inclusive prefixes in place; *out = the sum.
-__global__ __launch_bounds__(kScanBlock) void rec_carry_kernel(uint32_t* __restrict__ tcount, uint64_t ntiles,
-                                                               uint32_t* __restrict__ d_count) {
-    __shared__ uint32_t part[kScanWaves];
-    uint32_t carry = 0;
-    for (uint64_t base = 0; base < ntiles; base += kScanBlock) {
-        const uint64_t t = base + threadIdx.x;
-        const uint32_t v = t < ntiles ? tcount[t] : 0u;
-        uint32_t total;
-        const uint32_t incl = carry + block_inclusive_scan<kScanWaves>(v, part, &total);
-        if (t < ntiles) tcount[t] = incl;
-        carry += total;
+    __device__ __forceinline__ bool operator()(uint64_t i, Rec* out) const {
+        if (i >= n) return false;
+        if (!wire::status_passes(status[i], need, reject)) return false;
+        wire::Ipv4View ip;
+        const bool trusted = wire::ipv4_view(bytes, bytes_len, off[i], len[i], &ip);
+        const uint32_t frag = ip.frag;
+        const uint32_t offset = (frag & 0x1FFFu) << 3;
+        // `|`: one branch for both tests, so that the fragment word's load is not sunk behind the first
+        // one (a memory round trip: 74 -> 93 us for the records of 1 Mi fragments)
+        if (!trusted | (offset + ip.ip_len > 65535u)) return false;
+        const uint32_t dst = ip.dst();
+        if (host != 0 && dst != host) return false;
+        out->frame = reinterpret_cast<uint64_t>(ip.h);
+        out->addr = uint64_t(ip.src()) | (uint64_t(dst) << 32);
+        out->w2 = uint64_t(ip.id()) | (uint64_t(ip.proto()) << 16) | (uint64_t((frag >> 13) & 1u) << 24) |
+                  (uint64_t(offset) << 32) | (uint64_t(ip.hdr_len) << 48);
+        out->w3 = uint64_t(ip.ip_len - ip.hdr_len) | (uint64_t(tag) << 32);
+        return true;
     }
-    if (threadIdx.x == 0) *d_count = carry;
-}
 
-__global__ __launch_bounds__(kScanBlock) void rec_place_kernel(Frames F, const uint32_t* __restrict__ tcount,
-                                                               sccsum_frag_rec* __restrict__ d_rec) {
-    __shared__ uint32_t part[kScanWaves];
-    Rec r;
-    const bool ok = frame_record(F, uint64_t(blockIdx.x) * kScanTile + threadIdx.x, &r);
-    const uint32_t a = ok ? 1u : 0u;
-    uint32_t total;
-    const uint32_t incl = block_inclusive_scan<kScanWaves>(a, part, &total);
-    const uint32_t base = blockIdx.x ? tcount[blockIdx.x - 1] : 0u;
-    if (ok) store_rec(d_rec, uint64_t(base) + incl - 1u, r);
-}
+    static __device__ __forceinline__ void store(Out* __restrict__ d_rec, uint64_t pos, const Rec& r) {
+        store_rec(d_rec, pos, r);
+    }
+};
 
 // ---------------------------------------------------------------- sort
 
@@ -232,28 +186,16 @@ __global__ __launch_bounds__(kSortBlock) void sort_count_kernel(const uint64_t* 
                                                                 uint32_t mask, uint32_t* __restrict__ counts,
                                                                 uint32_t pitch) {
     __shared__ uint32_t hist[kDigits];
-    hist[threadIdx.x] = 0;
+    bucket_pass::hist_clear(hist);
     __syncthreads();
     const uint32_t first = blockIdx.x * kSortTile;
     uint64_t k[kSortRounds];
     uint32_t d[kSortRounds];
     tile_digits(key, m, first, shift, mask, k, d);
 #pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
-        const bool valid = first + r * kSortBlock + threadIdx.x < m;
-        const uint64_t peers = match_bucket(d[r], valid);
-        // one LDS add per distinct digit of the wave: only a count comes out
-        if (valid && (peers & lanes_below()) == 0) atomicAdd(&hist[d[r]], static_cast<uint32_t>(__popcll(peers)));
-    }
+    for (int r = 0; r < kSortRounds; ++r) bucket_pass::hist_add(hist, d[r], first + r * kSortBlock + threadIdx.x < m);
     __syncthreads();
-    counts[uint64_t(threadIdx.x) * pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-// One block (one wave) per digit: its row of per-tile counts scanned in place.
-__global__ __launch_bounds__(kWave) void sort_scan_kernel(uint32_t* __restrict__ counts, uint32_t ntiles, uint32_t pitch,
-                                                          uint32_t* __restrict__ totals) {
-    const uint32_t sum = scan_row(counts, blockIdx.x, ntiles, pitch);
-    if (lane_id() == 0) totals[blockIdx.x] = sum;
+    bucket_pass::hist_store(hist, kDigits, counts, pitch);
 }
 
 __global__ __launch_bounds__(kSortBlock) void sort_scatter_kernel(const uint64_t* __restrict__ key,
@@ -262,27 +204,17 @@ __global__ __launch_bounds__(kSortBlock) void sort_scatter_kernel(const uint64_t
                                                                   uint32_t pitch, const uint32_t* __restrict__ totals,
                                                                   uint64_t* __restrict__ key_out,
                                                                   uint32_t* __restrict__ idx_out) {
-    // cnt[slot][digit]: records of the digit in (round, wave) pair `slot`, then their offset inside the
-    // tile (at most 2048: 16 bits); base[digit]: where the tile's records of the digit start
-    __shared__ uint16_t cnt[kSlots][kDigits];
+    // base[digit]: where the tile's records of the digit start
     __shared__ uint32_t base[kDigits];
     __shared__ uint32_t part[kSortWaves];
-    const uint32_t wave = threadIdx.x / kWave;
-    {
-        // the digit's first position: the exclusive scan of the totals, one digit per thread
-        const uint32_t t = totals[threadIdx.x];
-        uint32_t all;
-        const uint32_t incl = block_inclusive_scan<kSortWaves>(t, part, &all);
-#pragma unroll
-        for (int s = 0; s < kSlots; ++s) cnt[s][threadIdx.x] = 0;
-        base[threadIdx.x] = incl - t + counts[uint64_t(threadIdx.x) * pitch + blockIdx.x];
-    }
+    bucket_pass::TileRank<kSortWaves, kSortRounds, kDigits> rank;
+    bucket_pass::digit_base<kSortWaves>(base, totals, counts, pitch, part);
+    rank.clear(kDigits);
     __syncthreads();
     const uint32_t first = blockIdx.x * kSortTile;
     uint64_t k[kSortRounds];
     uint32_t d[kSortRounds];
     uint32_t src[kSortRounds];
-    uint32_t rank[kSortRounds];
     tile_digits(key, m, first, shift, mask, k, d);
 #pragma unroll
     for (int r = 0; r < kSortRounds; ++r) {
@@ -290,28 +222,15 @@ __global__ __launch_bounds__(kSortBlock) void sort_scatter_kernel(const uint64_t
         src[r] = i < m ? idx[i] : 0u;
     }
 #pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
-        const bool valid = first + r * kSortBlock + threadIdx.x < m;
-        const uint64_t peers = match_bucket(d[r], valid);
-        rank[r] = static_cast<uint32_t>(__popcll(peers & lanes_below()));
-        if (valid && rank[r] == 0) cnt[r * kSortWaves + wave][d[r]] = static_cast<uint16_t>(__popcll(peers));
-    }
+    for (int r = 0; r < kSortRounds; ++r) rank.mark(r, d[r], first + r * kSortBlock + threadIdx.x < m);
     __syncthreads();
-    {
-        uint32_t run = 0;
-#pragma unroll
-        for (int s = 0; s < kSlots; ++s) {
-            const uint32_t c = cnt[s][threadIdx.x];
-            cnt[s][threadIdx.x] = static_cast<uint16_t>(run);
-            run += c;
-        }
-    }
+    rank.scan(kDigits);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < kSortRounds; ++r) {
         const uint32_t i = first + r * kSortBlock + threadIdx.x;
         if (i < m) {
-            const uint32_t pos = base[d[r]] + cnt[r * kSortWaves + wave][d[r]] + rank[r];
+            const uint32_t pos = base[d[r]] + rank.offset(r, d[r]);
             if (pos < m) {  // always true: the counts are this pass's own
                 key_out[pos] = k[r];
                 idx_out[pos] = src[r];
@@ -360,30 +279,14 @@ __device__ __forceinline__ Seg seg_join(const Seg& a, const Seg& b) {  // a befo
     return Seg{a.hp, a.fl | b.fl, a.arr > b.arr ? a.arr : b.arr};
 }
 
-__device__ __forceinline__ Seg seg_shfl_up(const Seg& v, int d) {
-    return Seg{__shfl_up(v.hp, d, kWave), __shfl_up(v.fl, d, kWave), __shfl_up(v.arr, d, kWave)};
+__device__ __forceinline__ Seg shfl_up(const Seg& v, int d) {
+    return Seg{wave_scan::shfl_up(v.hp, d), wave_scan::shfl_up(v.fl, d), wave_scan::shfl_up(v.arr, d)};
 }
 
 // Inclusive segmented scan over the 1024 threads of a block; *total = the block's.
 __device__ __forceinline__ Seg seg_block_scan(Seg v, Seg* part, Seg* total) {
-    const uint32_t wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const Seg o = seg_shfl_up(v, d);
-        if (lane_id() >= static_cast<uint32_t>(d)) v = seg_join(o, v);
-    }
-    __syncthreads();  // the last call's readers are done with part
-    if (lane_id() == kWave - 1) part[wave] = v;
-    __syncthreads();
-    Seg before{0, 0, 0}, all{0, 0, 0};
-#pragma unroll
-    for (int w = 0; w < kScanWaves; ++w) {
-        const Seg p = part[w];
-        if (static_cast<uint32_t>(w) < wave) before = seg_join(before, p);
-        all = seg_join(all, p);
-    }
-    *total = all;
-    return seg_join(before, v);
+    return wave_scan::block_scan_serial<kScanWaves>(
+        v, Seg{0, 0, 0}, part, total, [](const Seg& a, const Seg& b) { return seg_join(a, b); });
 }
 
 __device__ __forceinline__ Seg seg_of(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ idx, uint32_t m,
@@ -580,12 +483,6 @@ __device__ __forceinline__ uint32_t toeplitz96(const Rss& P, uint32_t d0, uint32
     return h;
 }
 
-__device__ __forceinline__ uint32_t pseudo_seed(uint32_t src, uint32_t dst, uint32_t proto, uint32_t len16) {
-    uint64_t s = uint64_t(src) + dst + proto + len16;
-    while (s >> 16) s = (s & 0xFFFFu) + (s >> 16);
-    return static_cast<uint32_t>(s);
-}
-
 struct Dgrams {
     uint32_t* first;
     uint64_t* off;
@@ -758,7 +655,7 @@ Layout layout(uint64_t m) {
         return here;
     };
     L.sort_tiles = static_cast<uint32_t>(tiles_of(m, kSortTile));
-    L.pitch = (L.sort_tiles + 3u) & ~3u;
+    L.pitch = bucket_pass::pitch_of(L.sort_tiles);
     L.scan_tiles = static_cast<uint32_t>(tiles_of(m, kScanTile));
     L.head = take(16);
     for (int k = 0; k < 2; ++k) L.key[k] = take(8 * m);
@@ -781,14 +678,6 @@ Layout layout(uint64_t m) {
     L.t2 = take(8 * uint64_t(L.scan_tiles));
     L.bytes = at;
     return L;
-}
-
-// The devices of a launch on `st`: the stream's must be the current one, where the data lies.
-int stream_ok(hipStream_t st) {
-    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
-    const hipError_t e = host_launch::stream_devices(st, &dev, &sd);
-    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
-    return sd != dev ? SCCSUM_EINVAL : SCCSUM_OK;
 }
 
 }  // namespace reasm
@@ -818,22 +707,12 @@ int sccsum_ipv4_frag_records(const void* d_bytes, uint64_t bytes_len, const uint
         if (misaligned(d_off, 8) || misaligned(d_len, 4) || misaligned(d_rec, 8)) return SCCSUM_EINVAL;
     }
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rc = stream_ok(st);
+    const int rc = stream_ok(st, -1);
     if (rc != SCCSUM_OK) return rc;
-    const Frames F{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, d_status, n, need, reject,
-                   host_address, tag};
-    const uint64_t ntiles = tiles_of(n, kScanTile);
-    uint32_t* const tcount = static_cast<uint32_t*>(d_workspace);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(rec_tile_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kScanBlock), 0, st, F, tcount);
-        if (e != hipSuccess) return static_cast<int>(e);
-    }
-    e = launch_kernel(rec_carry_kernel, dim3(1), dim3(kScanBlock), 0, st, tcount, ntiles, d_count);
-    if (e != hipSuccess || !ntiles) return static_cast<int>(e);
-    e = launch_kernel(rec_place_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kScanBlock), 0, st, F,
-                      static_cast<const uint32_t*>(tcount), d_rec);
-    return static_cast<int>(e);
+    const FrameRecord F{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, d_status, n, need, reject,
+                        host_address, tag};
+    return static_cast<int>(compact::run<kScanBlock>(st, F, tiles_of(n, kScanTile), static_cast<uint32_t*>(d_workspace),
+                                                     d_count, d_rec));
 }
 
 int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out_bytes, const uint8_t* key,
@@ -860,7 +739,7 @@ int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out
         }
     }
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rc = stream_ok(st);
+    const int rc = stream_ok(st, -1);
     if (rc != SCCSUM_OK) return rc;
     if (m == 0) {
         return static_cast<int>(
@@ -886,7 +765,7 @@ int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out
         const uint32_t* const iin = u32(L.idx[p & 1]);
         REASM_LAUNCH(sort_count_kernel, sort, dim3(kSortBlock), 0, st, kin, n, kPassShift[p], kPassMask[p],
                      u32(L.counts), L.pitch);
-        REASM_LAUNCH(sort_scan_kernel, dim3(kDigits), dim3(kWave), 0, st, u32(L.counts), L.sort_tiles, L.pitch,
+        REASM_LAUNCH(scan_rows_kernel<>, dim3(kDigits), dim3(kWave), 0, st, u32(L.counts), L.sort_tiles, L.pitch,
                      u32(L.totals));
         REASM_LAUNCH(sort_scatter_kernel, sort, dim3(kSortBlock), 0, st, kin, iin, n, kPassShift[p], kPassMask[p],
                      static_cast<const uint32_t*>(u32(L.counts)), L.pitch, static_cast<const uint32_t*>(u32(L.totals)),

@@ -42,11 +42,13 @@
 #include "sccsum.h"
 #include "sccsum_diag.h"
 #include "wave_scan.h"
+#include "wire.h"
 
 namespace send {
 
 using host_launch::launch_kernel;
 using host_launch::misaligned;
+using wire::tiles_of;
 
 constexpr int kWave = 64;
 constexpr int kTileBlock = 1024;                // threads of the count / scan / place kernels: one datagram each
@@ -66,8 +68,6 @@ constexpr uint64_t kNoCut = ~uint64_t(0);
 // tile {frames, bytes} (totals, then their exclusive scan), then every
 // datagram's first byte in the packed layout.
 constexpr uint64_t kWsHead = 2;
-
-__host__ __device__ inline uint64_t tiles_of(uint64_t n) { return (n + kSendTile - 1) / kSendTile; }
 
 __host__ __device__ inline bool needs_frag(uint32_t len, uint32_t proto, uint32_t mtu, uint32_t flags) {
     if (len + kIpHdr <= mtu) return false;
@@ -355,7 +355,7 @@ int sccsum_ipv4_send_plan(const sccsum_send_opts* opts, uint32_t l4_len, uint8_t
 }
 
 uint64_t sccsum_ipv4_send_workspace(uint64_t n) {
-    const uint64_t words = send::kWsHead + 2 * send::tiles_of(n) + n;
+    const uint64_t words = send::kWsHead + 2 * send::tiles_of(n, send::kSendTile) + n;
     return (words * 8 + 15) & ~uint64_t(15);
 }
 
@@ -393,7 +393,7 @@ int sccsum_ipv4_send(const sccsum_send_opts* opts, void* d_l4, uint64_t l4_bytes
     if (sd != dev) return SCCSUM_EINVAL;
 
     const Batch B{d_off, d_len, d_proto, l4_bytes_len, n, opts->mtu, opts->flags};
-    const uint64_t ntiles = tiles_of(n);
+    const uint64_t ntiles = tiles_of(n, kSendTile);
     uint64_t* const ws = static_cast<uint64_t*>(d_workspace);
     if (ntiles) {
         e = launch_kernel(send_count_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), 0, st, B, ws);

@@ -13,14 +13,14 @@
 //   steer_count_kernel    one block per tile of kSteerTile packets: destination
 //                         of every packet (-> d_cpu), per-bucket counts of the
 //                         tile -> workspace[bucket][tile]
-//   steer_scan_kernel     ONE block: per bucket an exclusive scan over the
-//                         tiles (in place), then the bucket bases -> d_first;
-//                         with more than 32 buckets steer_scan_rows_kernel (one
-//                         block per bucket) and steer_scan_totals_kernel instead
+//   bucket_pass's scan    ONE block (scan_kernel): per bucket an exclusive scan
+//                         over the tiles (in place), then the bucket bases ->
+//                         d_first; with more than 32 buckets scan_rows_kernel
+//                         (one block per bucket) and scan_totals_kernel instead
 //   steer_scatter_kernel  one block per tile: destinations recomputed, each
-//                         packet's rank inside its tile computed from wave
-//                         match masks and a per-wave count table, index stored
-//                         at d_first[bucket] + workspace[bucket][tile] + rank
+//                         packet's offset inside its tile (bucket_pass's
+//                         TileRank), index stored at d_first[bucket] +
+//                         workspace[bucket][tile] + offset
 // Bucket c < ncpu is shard c, bucket ncpu holds the dropped packets.  No
 // atomic decides a position: the only atomics are LDS adds into the count
 // kernel's histogram, whose sums do not depend on their order, so every
@@ -37,32 +37,26 @@
 #include "host_launch.h"
 #include "sccsum.h"
 #include "sccsum_diag.h"
-#include "wave_scan.h"
+#include "wire.h"
 
 namespace steer {
 
-using bucket_pass::lanes_below;
-using bucket_pass::match_bucket;  // a packet's peers of the same bucket in its wave
-using bucket_pass::scan_row;      // one bucket's row of per-tile counts, scanned in place
+using bucket_pass::pitch_of;
 using host_launch::launch_kernel;
 using host_launch::misaligned;
-using wave_scan::lane_id;
-using wave_scan::wave_inclusive_scan;
+using wire::kMaxDevices;
+using wire::status_passes;
 
 constexpr int kBlock = 256;              // threads per block of the count / scatter kernels
 constexpr int kWave = 64;
 constexpr int kWaves = kBlock / kWave;
 constexpr int kRounds = 8;               // packets per thread: round r of a tile is its packets [256 r, 256 r + 256)
 constexpr uint32_t kSteerTile = kBlock * kRounds;
-constexpr int kSlots = kRounds * kWaves; // (round, wave) pairs of a tile, in packet order
 constexpr int kMaxBuckets = 256;         // ncpu <= 255 shards + the drop bucket
-constexpr int kScanBlock = 1024;
-constexpr int kScanWaves = kScanBlock / kWave;
-constexpr uint32_t kScanOneBlockMax = 2 * kScanWaves;  // buckets the one-block scan takes (two rows per wave)
+constexpr int kScanBlock = 1024;         // threads of the one-block scan
 constexpr uint32_t kRetaSize = 128;      // std::array<uint8_t, 128> (net.hh, qp::_sw_reta)
 constexpr uint32_t kMaxRedir = 512;
 constexpr uint32_t kMaxQueues = 256;
-constexpr int kMaxDevices = 64;
 
 // What the kernels need of a map (by value in the launch).  `reta` points at
 // the first row the launch uses: rows == 0 means every packet goes to `fixed`
@@ -97,7 +91,7 @@ __device__ __forceinline__ void load_tables(const Params& P, uint8_t* lds) {
 // Bucket of one packet: ncpu for a dropped one.
 __device__ __forceinline__ uint32_t bucket_of(const Params& P, const uint8_t* lds, uint32_t hash, uint32_t st,
                                               bool has_status) {
-    if (has_status && ((st & P.need) != P.need || (st & P.reject) != 0)) return P.ncpu;
+    if (has_status && !status_passes(st, P.need, P.reject)) return P.ncpu;
     if (P.rows == 0) return P.fixed;
     uint32_t q = 0;
     if (P.rows > 1) {
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void steer_count_kernel(const uint32_t* __r
     uint8_t* const lds = reinterpret_cast<uint8_t*>(steer_dyn_lds);
     const uint32_t buckets = P.ncpu + 1;
     load_tables(P, lds);
-    hist[threadIdx.x] = 0;
+    bucket_pass::hist_clear(hist);
     __syncthreads();
     const uint64_t first = uint64_t(blockIdx.x) * kSteerTile;
     uint32_t b[kRounds];
@@ -142,58 +136,11 @@ __global__ __launch_bounds__(kBlock) void steer_count_kernel(const uint32_t* __r
     for (int r = 0; r < kRounds; ++r) {
         const uint64_t i = first + uint64_t(r) * kBlock + threadIdx.x;
         const bool valid = i < n;
-        const uint64_t m = match_bucket(b[r], valid);
-        // one LDS add per distinct bucket of the wave: only a count comes out
-        if (valid && (m & lanes_below()) == 0) atomicAdd(&hist[b[r]], static_cast<uint32_t>(__popcll(m)));
+        bucket_pass::hist_add(hist, b[r], valid);
         if (valid && d_cpu) d_cpu[i] = b[r] == P.ncpu ? uint8_t(0xFF) : static_cast<uint8_t>(b[r]);
     }
     __syncthreads();
-    if (threadIdx.x < buckets) ws[uint64_t(threadIdx.x) * tile_pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-// One wave: the bucket totals scanned into d_first (ncpu + 2 entries).
-__device__ __forceinline__ void scan_totals(const uint32_t* total, uint32_t buckets, uint32_t* __restrict__ d_first) {
-    const uint32_t lane = lane_id();
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < buckets; base += kWave) {
-        const uint32_t b = base + lane;
-        const uint32_t c = b < buckets ? total[b] : 0u;
-        const uint32_t incl = wave_inclusive_scan(c);
-        if (b < buckets) d_first[b] = carry + incl - c;
-        carry += __shfl(incl, kWave - 1, kWave);
-    }
-    if (lane == 0) d_first[buckets] = carry;
-}
-
-// Few buckets (at most kScanOneBlockMax): ONE block does both, wave w taking
-// the rows of buckets w, w + 16, ...
-__global__ __launch_bounds__(kScanBlock) void steer_scan_kernel(uint32_t* __restrict__ ws, uint32_t ntiles,
-                                                                uint32_t tile_pitch, uint32_t buckets,
-                                                                uint32_t* __restrict__ d_first) {
-    __shared__ uint32_t total[kMaxBuckets];
-    const uint32_t wave = threadIdx.x / kWave;
-    for (uint32_t b = wave; b < buckets; b += kScanWaves) {
-        const uint32_t sum = scan_row(ws, b, ntiles, tile_pitch);
-        if (lane_id() == 0) total[b] = sum;
-    }
-    __syncthreads();
-    if (wave == 0) scan_totals(total, buckets, d_first);
-}
-
-// Many buckets: one block (one wave) per bucket scans its row and leaves the
-// total behind the rows; a second launch of one wave scans the totals.  One
-// compute unit alone takes 24 us for the 257 rows of 512 tiles of a
-// 1 Mi-packet batch at 255 shards, whether or not its loads are batched
-// (DESIGN.md §5.12): the rows are spread over the device instead.
-__global__ __launch_bounds__(kWave) void steer_scan_rows_kernel(uint32_t* __restrict__ ws, uint32_t ntiles,
-                                                                uint32_t tile_pitch, uint32_t* __restrict__ totals) {
-    const uint32_t sum = scan_row(ws, blockIdx.x, ntiles, tile_pitch);
-    if (lane_id() == 0) totals[blockIdx.x] = sum;
-}
-
-__global__ __launch_bounds__(kWave) void steer_scan_totals_kernel(const uint32_t* __restrict__ totals, uint32_t buckets,
-                                                                  uint32_t* __restrict__ d_first) {
-    scan_totals(totals, buckets, d_first);
+    bucket_pass::hist_store(hist, buckets, ws, tile_pitch);
 }
 
 __global__ __launch_bounds__(kBlock) void steer_scatter_kernel(const uint32_t* __restrict__ d_hash,
@@ -201,48 +148,28 @@ __global__ __launch_bounds__(kBlock) void steer_scatter_kernel(const uint32_t* _
                                                                const uint32_t* __restrict__ ws, uint32_t tile_pitch,
                                                                const uint32_t* __restrict__ d_first,
                                                                uint32_t* __restrict__ d_order, Params P) {
-    // cnt[slot][bucket]: packets of the bucket in (round, wave) pair `slot`, then
-    // their offset inside the tile (at most 2048: 16 bits); base[bucket]: where
-    // the tile's packets of the bucket start in d_order
-    __shared__ uint16_t cnt[kSlots][kMaxBuckets];
+    // base[bucket]: where the tile's packets of the bucket start in d_order
     __shared__ uint32_t base[kMaxBuckets];
+    bucket_pass::TileRank<kWaves, kRounds, kMaxBuckets> rank;
     uint8_t* const lds = reinterpret_cast<uint8_t*>(steer_dyn_lds);
     const uint32_t buckets = P.ncpu + 1;
-    const uint32_t wave = threadIdx.x / kWave;
     load_tables(P, lds);
-    if (threadIdx.x < buckets) {
-#pragma unroll
-        for (int s = 0; s < kSlots; ++s) cnt[s][threadIdx.x] = 0;
-        base[threadIdx.x] = d_first[threadIdx.x] + ws[uint64_t(threadIdx.x) * tile_pitch + blockIdx.x];
-    }
+    rank.clear(buckets);
+    bucket_pass::bucket_base(base, buckets, d_first, ws, tile_pitch);
     __syncthreads();
     const uint64_t first = uint64_t(blockIdx.x) * kSteerTile;
     uint32_t b[kRounds];
-    uint32_t rank[kRounds];
     tile_buckets(P, lds, d_hash, d_status, n, first, b);
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const bool valid = first + uint64_t(r) * kBlock + threadIdx.x < n;
-        const uint64_t m = match_bucket(b[r], valid);
-        rank[r] = static_cast<uint32_t>(__popcll(m & lanes_below()));
-        if (valid && rank[r] == 0) cnt[r * kWaves + wave][b[r]] = static_cast<uint16_t>(__popcll(m));
-    }
+    for (int r = 0; r < kRounds; ++r) rank.mark(r, b[r], first + uint64_t(r) * kBlock + threadIdx.x < n);
     __syncthreads();
-    if (threadIdx.x < buckets) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int s = 0; s < kSlots; ++s) {
-            const uint32_t c = cnt[s][threadIdx.x];
-            cnt[s][threadIdx.x] = static_cast<uint16_t>(run);
-            run += c;
-        }
-    }
+    rank.scan(buckets);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
         const uint64_t i = first + uint64_t(r) * kBlock + threadIdx.x;
         if (i < n) {
-            const uint64_t pos = uint64_t(base[b[r]]) + cnt[r * kWaves + wave][b[r]] + rank[r];
+            const uint64_t pos = uint64_t(base[b[r]]) + rank.offset(r, b[r]);
             if (pos < n) d_order[pos] = static_cast<uint32_t>(i);  // always true for consistent inputs
         }
     }
@@ -391,8 +318,7 @@ int sccsum_steer_destroy(sccsum_steer* s) {
 
 uint64_t sccsum_steer_workspace(const sccsum_steer* s, uint64_t n) {
     if (!s) return 0;
-    const uint64_t ntiles = (n + steer::kSteerTile - 1) / steer::kSteerTile;
-    const uint64_t pitch = (ntiles + 3) & ~uint64_t(3);
+    const uint64_t pitch = steer::pitch_of(wire::tiles_of(n, steer::kSteerTile));
     // the per-tile counts [ncpu + 1][pitch], then the bucket totals of the many-bucket scan
     return uint64_t(s->map.ncpu + 1) * pitch * 4u + steer::kMaxBuckets * 4u;
 }
@@ -440,8 +366,8 @@ int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const ui
     if (e != hipSuccess) return static_cast<int>(e);
     if (dev != s->device) return SCCSUM_EINVAL;
 
-    const uint32_t ntiles = static_cast<uint32_t>((n + kSteerTile - 1) / kSteerTile);
-    const uint32_t pitch = (ntiles + 3u) & ~3u;
+    const uint32_t ntiles = static_cast<uint32_t>(wire::tiles_of(n, kSteerTile));
+    const uint32_t pitch = pitch_of(ntiles);
     const uint32_t buckets = P.ncpu + 1;
     uint32_t* const ws = static_cast<uint32_t*>(d_workspace);
     const size_t lds = size_t(P.rows) * kRetaSize + (P.rows > 1 ? ((P.redir_size + 15u) & ~15u) : 0u);
@@ -450,16 +376,8 @@ int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const ui
                           P);
         if (e != hipSuccess) return static_cast<int>(e);
     }
-    if (buckets <= kScanOneBlockMax || ntiles == 0) {
-        e = launch_kernel(steer_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, ws, ntiles, pitch, buckets, d_first);
-    } else {
-        uint32_t* const totals = ws + uint64_t(buckets) * pitch;
-        e = launch_kernel(steer_scan_rows_kernel, dim3(buckets), dim3(kWave), 0, st, ws, ntiles, pitch, totals);
-        if (e == hipSuccess) {
-            e = launch_kernel(steer_scan_totals_kernel, dim3(1), dim3(kWave), 0, st, static_cast<const uint32_t*>(totals),
-                              buckets, d_first);
-        }
-    }
+    e = bucket_pass::scan_buckets<kScanBlock, kMaxBuckets>(st, ws, ntiles, pitch, buckets, d_first,
+                                                           ws + uint64_t(buckets) * pitch);
     if (e != hipSuccess) return static_cast<int>(e);
     if (ntiles && d_order) {
         e = launch_kernel(steer_scatter_kernel, dim3(ntiles), dim3(kBlock), lds, st, d_hash, d_status, n,

@@ -46,67 +46,48 @@
 #include "host_launch.h"
 #include "sccsum.h"
 #include "wave_scan.h"
+#include "wire.h"
 
 namespace tcp {
 
-using bucket_pass::lanes_below;
-using bucket_pass::match_bucket;
-using bucket_pass::scan_row;
+using bucket_pass::kDigits;
+using bucket_pass::scan_rows_kernel;
 using host_launch::launch_kernel;
 using host_launch::misaligned;
+using host_launch::stream_ok;
 using wave_scan::block_inclusive_scan;
-using wave_scan::lane_id;
+using wire::be16_at;
+using wire::be32_at;
+using wire::fold16;
+using wire::kMaxDevices;
+using wire::pseudo_seed;
+using wire::tiles_of;
 
 constexpr int kWave = 64;
 constexpr int kBlock = 1024;                 // threads of every tile kernel: one segment each
 constexpr int kWaves = kBlock / kWave;
 constexpr uint32_t kTile = kBlock;           // sccsum_eth_tile_packets()
-constexpr uint32_t kDigits = 256;
 constexpr uint32_t kPorts = 65536;
-constexpr uint32_t kIpHdrMin = 20;
 constexpr uint32_t kTcpHdr = 20;             // tcp_hdr::len
 constexpr uint32_t kProtoTcp = 6;
 constexpr uint32_t kMaxL4 = 65515;           // sccsum_ipv4_send's limit
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kRst = 4u, kSyn = 2u, kAck = 16u;
 constexpr int kFlatBlock = 256;
-constexpr int kMaxDevices = 64;
 constexpr int kHostOnly = -1;                // device of a table that has no device copy
 constexpr uint32_t kMaxConns = SCCSUM_TCP_MAX_CONNS;
 
 static_assert(sizeof(sccsum_tcp_seg) == 32 && sizeof(sccsum_tcp_out) == 24 && sizeof(sccsum_tcp_conn) == 12, "layout");
 
-__host__ __device__ inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
-
-__device__ __forceinline__ uint32_t be16_at(const uint8_t* p) { return (uint32_t(p[0]) << 8) | p[1]; }
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
-    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3];
-}
 __device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-
-__host__ __device__ inline uint32_t fold16(uint64_t s) {
-    while (s >> 16) s = (s & 0xFFFFu) + (s >> 16);
-    return static_cast<uint32_t>(s);
-}
-
-// ipv4_traits::tcp_pseudo_header_checksum folded, as sccsum_pseudo_seed (ip.hh:70-75).
-__host__ __device__ inline uint32_t pseudo_seed(uint32_t src, uint32_t dst, uint32_t proto, uint32_t len16) {
-    return fold16(uint64_t(src) + dst + proto + len16);
-}
 
 // ---------------------------------------------------------------- the connection table
 
-// The home slot of a connid: the three key words mixed as murmur3's fmix32 mixes one.
+// The home slot of a connid: the three key words mixed, then murmur3's finalizer.
 __host__ __device__ inline uint32_t hash_of(uint32_t local_ip, uint32_t foreign_ip, uint32_t ports) {
     uint32_t h = local_ip * 0x9E3779B1u;
     h = (h ^ foreign_ip) * 0x85EBCA6Bu;
-    h ^= ports;
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
+    return wire::fmix32(h ^ ports);
 }
 
 // Linear probing from the home slot: the connection index, or kNone at the
@@ -169,23 +150,21 @@ __device__ __forceinline__ Item decode(const Decode& D, uint64_t j) {
     const uint32_t l = D.len[i];
     const uint32_t st = D.status[i];
     it.pay_off = o;
-    if ((st & D.need) != D.need || (st & D.reject) != 0) return it;
-    if (o > D.bytes_len || l > D.bytes_len - o || l < kIpHdrMin) return it;
-    const uint8_t* const h = D.bytes + o;
-    const uint32_t ihl4 = 4u * (h[0] & 0xFu);
-    const uint32_t ip_len = be16_at(h + 2);
-    if (l < ip_len || ihl4 > ip_len) return it;
-    if ((be16_at(h + 6) & 0x3FFFu) != 0) return it;       // MF or a fragment offset
-    const uint32_t dst = be32_at(h + 16);
+    if (!wire::status_passes(st, D.need, D.reject)) return it;
+    wire::Ipv4View ip;
+    if (!wire::ipv4_view(D.bytes, D.bytes_len, o, l, &ip)) return it;
+    if ((ip.frag & 0x3FFFu) != 0) return it;              // MF or a fragment offset
+    const uint32_t dst = ip.dst();
     if (D.host != 0 && dst != D.host) return it;
-    if (h[9] != kProtoTcp) return it;
-    const uint32_t E = ip_len - ihl4;                     // the trim to the IP total length
+    if (ip.proto() != kProtoTcp) return it;
+    const uint32_t ihl4 = ip.hdr_len;
+    const uint32_t E = ip.ip_len - ihl4;                  // the trim to the IP total length
     it.cls = SCCSUM_TCP_SHORT;
     if (E < kTcpHdr) return it;                           // get_header(0, tcp_hdr::len) is null
-    const uint8_t* const t = h + ihl4;
+    const uint8_t* const t = ip.h + ihl4;
     const uint32_t H = 4u * (uint32_t(t[12]) >> 4);
     if (H < kTcpHdr) return it;
-    const uint32_t src = be32_at(h + 12);
+    const uint32_t src = ip.src();
     const uint32_t sport = be16_at(t), dport = be16_at(t + 2);
     const uint32_t flags = t[13];
     const uint32_t c = probe(D.slots, D.mask, dst, src, (dport << 16) | sport);
@@ -226,18 +205,12 @@ __device__ __forceinline__ void store_item(uint4* __restrict__ rec, uint64_t j, 
                                 it.dport | (it.flags << 16) | (it.hdr_len << 24));
 }
 
-// One LDS add per distinct digit of the wave: only a count comes out.
-__device__ __forceinline__ void tile_hist(uint32_t* hist, uint32_t d, bool valid) {
-    const uint64_t m = match_bucket(d, valid);
-    if (valid && (m & lanes_below()) == 0) atomicAdd(&hist[d], static_cast<uint32_t>(__popcll(m)));
-}
-
 __global__ __launch_bounds__(kBlock) void decode_kernel(Decode D, uint8_t* __restrict__ d_class,
                                                         uint4* __restrict__ rec, uint2* __restrict__ addr,
                                                         uint2* __restrict__ kv, uint32_t* __restrict__ counts,
                                                         uint32_t pitch) {
     __shared__ uint32_t hist[kDigits];
-    if (threadIdx.x < kDigits) hist[threadIdx.x] = 0;
+    bucket_pass::hist_clear(hist);
     __syncthreads();
     const uint64_t j = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = j < D.n;
@@ -250,9 +223,9 @@ __global__ __launch_bounds__(kBlock) void decode_kernel(Decode D, uint8_t* __res
         kv[j] = make_uint2(key, static_cast<uint32_t>(j));
         if (d_class) d_class[j] = static_cast<uint8_t>(it.cls);
     }
-    tile_hist(hist, key & 0xFFu, valid);
+    bucket_pass::hist_add(hist, key & 0xFFu, valid);
     __syncthreads();
-    if (threadIdx.x < kDigits) counts[uint64_t(threadIdx.x) * pitch + blockIdx.x] = hist[threadIdx.x];
+    bucket_pass::hist_store(hist, kDigits, counts, pitch);
 }
 
 // ---------------------------------------------------------------- rx: one radix pass
@@ -260,62 +233,38 @@ __global__ __launch_bounds__(kBlock) void decode_kernel(Decode D, uint8_t* __res
 __global__ __launch_bounds__(kBlock) void sort_count_kernel(const uint2* __restrict__ kv, uint64_t n, int shift,
                                                             uint32_t* __restrict__ counts, uint32_t pitch) {
     __shared__ uint32_t hist[kDigits];
-    if (threadIdx.x < kDigits) hist[threadIdx.x] = 0;
+    bucket_pass::hist_clear(hist);
     __syncthreads();
     const uint64_t p = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = p < n;
     const uint32_t key = valid ? kv[p].x : 0u;
-    tile_hist(hist, (key >> shift) & 0xFFu, valid);
+    bucket_pass::hist_add(hist, (key >> shift) & 0xFFu, valid);
     __syncthreads();
-    if (threadIdx.x < kDigits) counts[uint64_t(threadIdx.x) * pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-// One block (one wave) per digit: its row of per-tile counts scanned in place.
-__global__ __launch_bounds__(kWave) void scan_rows_kernel(uint32_t* __restrict__ counts, uint32_t ntiles, uint32_t pitch,
-                                                          uint32_t* __restrict__ totals) {
-    const uint32_t sum = scan_row(counts, blockIdx.x, ntiles, pitch);
-    if (lane_id() == 0) totals[blockIdx.x] = sum;
+    bucket_pass::hist_store(hist, kDigits, counts, pitch);
 }
 
 // Stable: a pair's position is its digit's base, the pairs of the digit in the
-// tiles before (counts), in the waves before (cnt) and in the lanes below (rank).
+// tiles before (counts), and its offset among them inside the tile.
 __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(const uint2* __restrict__ kv, uint64_t n, int shift,
                                                               const uint32_t* __restrict__ counts, uint32_t pitch,
                                                               const uint32_t* __restrict__ totals,
                                                               uint2* __restrict__ kv_out) {
-    __shared__ uint32_t cnt[kWaves][kDigits];
     __shared__ uint32_t base[kDigits];
     __shared__ uint32_t part[kWaves];
-    const uint32_t wave = threadIdx.x / kWave;
-    {
-        // the digit's first position: the exclusive scan of the totals, one digit per thread
-        const uint32_t t = threadIdx.x < kDigits ? totals[threadIdx.x] : 0u;
-        uint32_t all;
-        const uint32_t incl = block_inclusive_scan<kWaves>(t, part, &all);
-        for (uint32_t k = threadIdx.x; k < kWaves * kDigits; k += kBlock) (&cnt[0][0])[k] = 0;
-        if (threadIdx.x < kDigits) base[threadIdx.x] = incl - t + counts[uint64_t(threadIdx.x) * pitch + blockIdx.x];
-    }
+    bucket_pass::TileRank<kWaves, 1, kDigits> rank;
+    bucket_pass::digit_base<kWaves>(base, totals, counts, pitch, part);
+    rank.clear(kDigits);
     __syncthreads();
     const uint64_t p = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = p < n;
     const uint2 e = valid ? kv[p] : make_uint2(0, 0);
     const uint32_t d = (e.x >> shift) & 0xFFu;
-    const uint64_t m = match_bucket(d, valid);
-    const uint32_t rank = static_cast<uint32_t>(__popcll(m & lanes_below()));
-    if (valid && rank == 0) cnt[wave][d] = static_cast<uint32_t>(__popcll(m));
+    rank.mark(0, d, valid);
     __syncthreads();
-    if (threadIdx.x < kDigits) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const uint32_t k = cnt[w][threadIdx.x];
-            cnt[w][threadIdx.x] = run;
-            run += k;
-        }
-    }
+    rank.scan(kDigits);
     __syncthreads();
     if (!valid) return;
-    const uint64_t pos = uint64_t(base[d]) + cnt[wave][d] + rank;
+    const uint64_t pos = uint64_t(base[d]) + rank.offset(0, d);
     if (pos < n) kv_out[pos] = e;  // always true: the counts are this pass's own
 }
 
@@ -529,15 +478,6 @@ __global__ __launch_bounds__(kFlatBlock) void send_kernel(Send S, SendOut O) {
 
 // ---------------------------------------------------------------- host side
 
-// The launches run on the stream's device, which must be `want` (the table's
-// device), or with want < 0 the calling thread's current one.
-int stream_ok(hipStream_t st, int want) {
-    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
-    const hipError_t e = host_launch::stream_devices(st, &dev, &sd);
-    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
-    return sd != (want < 0 ? dev : want) ? SCCSUM_EINVAL : SCCSUM_OK;
-}
-
 uint32_t slot_bits(uint32_t nconns) {
     uint32_t bits = 4;
     while ((uint64_t(1) << bits) < 2ull * nconns) ++bits;
@@ -608,8 +548,8 @@ struct Layout {
 
 Layout layout_of(uint64_t n) {
     Layout L{};
-    L.ntiles = static_cast<uint32_t>(tiles_of(n));
-    L.pitch = (L.ntiles + 3u) & ~3u;
+    L.ntiles = static_cast<uint32_t>(tiles_of(n, kTile));
+    L.pitch = bucket_pass::pitch_of(L.ntiles);
     uint64_t at = 0;
     L.rec = at;
     at += 32 * n;
@@ -771,7 +711,7 @@ int sccsum_tcp_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off
                                   L.pitch);
                 if (e != hipSuccess) break;
             }
-            e = launch_kernel(scan_rows_kernel, dim3(kDigits), dim3(kWave), 0, st, counts, L.ntiles, L.pitch, totals);
+            e = launch_kernel(scan_rows_kernel<>, dim3(kDigits), dim3(kWave), 0, st, counts, L.ntiles, L.pitch, totals);
             if (e != hipSuccess) break;
             e = launch_kernel(sort_scatter_kernel, tiles, block, 0, st, static_cast<const uint2*>(kv), n, 8 * p,
                               static_cast<const uint32_t*>(counts), L.pitch, static_cast<const uint32_t*>(totals),

@@ -43,13 +43,15 @@
 #include "host_launch.h"
 #include "sccsum.h"
 #include "wave_scan.h"
+#include "wire.h"
 
 namespace tcp_data {
 
 using host_launch::launch_kernel;
 using host_launch::misaligned;
+using host_launch::stream_ok;
 using wave_scan::block_inclusive_scan;
-using wave_scan::lane_id;
+using wire::tiles_of;
 
 constexpr int kWave = 64;
 constexpr int kBlock = 1024;                 // threads of every tile kernel: one record each
@@ -63,8 +65,6 @@ constexpr int kPosShift = 17;                // ... and that head's thread index
 
 static_assert(sizeof(sccsum_tcp_rcv) == 32 && sizeof(sccsum_tcp_rcv_run) == 32 && sizeof(sccsum_gather_desc) == 16,
               "layout");
-
-__host__ __device__ inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
 
 // ---------------------------------------------------------------- the delayed-ACK transducer
 
@@ -118,33 +118,11 @@ struct SegCount {
 __device__ __forceinline__ Elem shfl_up(const Elem& v, int d) {
     return Elem{wave_scan::shfl_up(v.sum, d), wave_scan::shfl_up(v.meta, d)};
 }
-__device__ __forceinline__ uint32_t shfl_up(uint32_t v, int d) { return wave_scan::shfl_up(v, d); }
 
-// Inclusive scan of an associative op (earlier first) over the block's threads;
-// *total = the block's aggregate.  `part`: LDS, one value per wave; the call may be repeated.
+// wave_scan's scan of an associative op over the block's 1024 threads.
 template <typename T, typename Op>
 __device__ __forceinline__ T block_scan(T v, const T& ident, T* part, T* total, Op op) {
-    const uint32_t wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const T o = shfl_up(v, d);
-        if (lane_id() >= static_cast<uint32_t>(d)) v = op(o, v);
-    }
-    __syncthreads();  // the last call's readers are done with part
-    if (lane_id() == kWave - 1) part[wave] = v;
-    __syncthreads();
-    if (wave == 0) {  // the waves' aggregates scanned in place by the first kWaves lanes of the first wave
-        T p = lane_id() < kWaves ? part[lane_id()] : ident;
-#pragma unroll
-        for (int d = 1; d < kWaves; d <<= 1) {
-            const T o = shfl_up(p, d);
-            if (lane_id() >= static_cast<uint32_t>(d)) p = op(o, p);
-        }
-        if (lane_id() < kWaves) part[lane_id()] = p;
-    }
-    __syncthreads();
-    *total = part[kWaves - 1];
-    return wave ? op(part[wave - 1], v) : v;
+    return wave_scan::block_scan<kWaves>(v, ident, part, total, op);
 }
 
 // ---------------------------------------------------------------- one record
@@ -289,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void sum_tile(In I, Ws W) {
 __global__ __launch_bounds__(kBlock) void sum_carry(In I, Ws W) {
     __shared__ Elem part[kWaves];
     __shared__ uint32_t hpart[kWaves];
-    const uint32_t ntiles = I.n ? static_cast<uint32_t>(tiles_of(bucket_end(I))) : 0u;
+    const uint32_t ntiles = I.n ? static_cast<uint32_t>(tiles_of(bucket_end(I), kTile)) : 0u;
     Elem carry{0, kIdent};
     uint32_t hcarry = 0;
     if (threadIdx.x == 0) {
@@ -370,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void stop_carry(In I, Ws W, Out O) {
     __shared__ uint64_t bpart[kWaves];
     __shared__ uint32_t shifted[kBlock];
     __shared__ uint32_t found;
-    const uint32_t ntiles = I.n ? static_cast<uint32_t>(tiles_of(bucket_end(I))) : 0u;
+    const uint32_t ntiles = I.n ? static_cast<uint32_t>(tiles_of(bucket_end(I), kTile)) : 0u;
     if (threadIdx.x == 0) found = 0;
     uint32_t ocarry = 0;
     uint64_t bcarry = 0, ccarry = 0;
@@ -535,7 +513,7 @@ struct Layout {
 
 Layout layout_of(uint64_t n) {
     Layout L{};
-    const uint64_t k = tiles_of(n) + 1;
+    const uint64_t k = tiles_of(n, kTile) + 1;
     uint64_t at = 0;
     uint64_t* const wide[] = {&L.agg_sum, &L.in_sum, &L.hbytes, &L.rbytes, &L.bytes_in, &L.cnt_in};
     for (uint64_t* w : wide) {
@@ -552,14 +530,6 @@ Layout layout_of(uint64_t n) {
     at += 16;
     L.bytes = (at + 15u) & ~uint64_t(15);
     return L;
-}
-
-// The launches run on the stream's device, which must be the calling thread's current one.
-int stream_ok(hipStream_t st) {
-    int dev = -1, sd = -1;
-    const hipError_t e = host_launch::stream_devices(st, &dev, &sd);
-    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
-    return sd != dev ? SCCSUM_EINVAL : SCCSUM_OK;
 }
 
 }  // namespace tcp_data
@@ -587,7 +557,7 @@ int sccsum_tcp_rx_data(const void* d_bytes, const sccsum_tcp_seg* d_seg, const u
         }
     }
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rc = stream_ok(st);
+    const int rc = stream_ok(st, -1);
     if (rc != SCCSUM_OK) return rc;
 
     const Layout L = layout_of(n);
@@ -600,7 +570,7 @@ int sccsum_tcp_rx_data(const void* d_bytes, const sccsum_tcp_seg* d_seg, const u
     const In I{reinterpret_cast<const uint2*>(d_seg), d_first, reinterpret_cast<const uint4*>(d_rcv), n, nconns};
     const Out O{reinterpret_cast<uint2*>(d_run), reinterpret_cast<uint2*>(d_desc), d_total, d_run_first, d_rx_total,
                 reinterpret_cast<uint64_t>(d_bytes), max_bytes, n < nconns ? n : nconns};
-    const dim3 tiles(static_cast<unsigned>(tiles_of(n))), block(kBlock);
+    const dim3 tiles(static_cast<unsigned>(tiles_of(n, kTile))), block(kBlock);
     hipError_t e = hipSuccess;
     if (n != 0) {
         e = launch_kernel(sum_tile, tiles, block, 0, st, I, W);

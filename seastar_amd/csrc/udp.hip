@@ -40,17 +40,20 @@
 #include "bucket_pass.h"
 #include "host_launch.h"
 #include "sccsum.h"
-#include "wave_scan.h"
+#include "wire.h"
 
 namespace udp {
 
-using bucket_pass::lanes_below;
-using bucket_pass::match_bucket;
-using bucket_pass::scan_row;
+using bucket_pass::pitch_of;
 using host_launch::launch_kernel;
 using host_launch::misaligned;
-using wave_scan::lane_id;
-using wave_scan::wave_inclusive_scan;
+using host_launch::stream_ok;
+using wire::be16_at;
+using wire::kIpHdrMin;
+using wire::kMaxDevices;
+using wire::pseudo_seed;
+using wire::status_passes;
+using wire::tiles_of;
 
 constexpr int kWave = 64;
 constexpr int kBlock = 1024;                 // threads of every tile kernel: one frame / datagram each
@@ -58,33 +61,16 @@ constexpr int kWaves = kBlock / kWave;
 constexpr uint32_t kTile = kBlock;           // sccsum_eth_tile_packets()
 constexpr uint32_t kMaxChannels = SCCSUM_UDP_MAX_CHANNELS;
 constexpr uint32_t kMaxBuckets = kMaxChannels + 1;  // the channels + the drop bucket
-constexpr uint32_t kScanOneBlockMax = 2 * kWaves;   // buckets the one-block scan takes (two rows per wave)
 constexpr uint32_t kTotals = 256;            // the bucket totals of the many-bucket scan, behind the rows
 constexpr uint32_t kPorts = 65536;
 constexpr uint32_t kUnbound = 0xFF;
-constexpr uint32_t kIpHdrMin = 20;
 constexpr uint32_t kUdpHdr = 8;              // sizeof(udp_hdr): src_port, dst_port, len, cksum
 constexpr uint32_t kProtoUdp = 17;
 constexpr uint32_t kMaxPayload = 65507;      // ipv4_send's 65 515 less the header
 constexpr int kSendBlock = 256;
-constexpr int kMaxDevices = 64;
 constexpr int kHostOnly = -1;                // device of a table that has no device copy
 
 static_assert(kMaxBuckets <= 256 && kMaxChannels <= SCCSUM_UDP_SKIP, "a bucket and a class are 8 bits");
-
-__host__ __device__ inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
-
-__device__ __forceinline__ uint32_t be16_at(const uint8_t* p) { return (uint32_t(p[0]) << 8) | p[1]; }
-__device__ __forceinline__ uint32_t be32_at(const uint8_t* p) {
-    return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3];
-}
-
-// ipv4_traits::udp_pseudo_header_checksum folded, as sccsum_pseudo_seed (ip.hh:70-75).
-__host__ __device__ inline uint32_t pseudo_seed(uint32_t src, uint32_t dst, uint32_t proto, uint32_t len16) {
-    uint64_t s = uint64_t(src) + dst + proto + len16;
-    while (s >> 16) s = (s & 0xFFFFu) + (s >> 16);
-    return static_cast<uint32_t>(s);
-}
 
 // ---------------------------------------------------------------- rx: what one item is
 
@@ -136,28 +122,23 @@ struct FramesDecode {
         if (i >= nbatch) return it;
         const uint64_t o = off[i];
         const uint32_t l = len[i];
-        const uint32_t st = status[i];
-        if ((st & need) != need || (st & reject) != 0) return it;
-        if (o > bytes_len || l > bytes_len - o || l < kIpHdrMin) return it;
-        const uint8_t* const h = bytes + o;
-        const uint32_t hdr_len = 4u * (h[0] & 0xFu);
-        const uint32_t ip_len = be16_at(h + 2);
-        if (l < ip_len || hdr_len > ip_len) return it;
-        if ((be16_at(h + 6) & 0x3FFFu) != 0) return it;       // MF or a fragment offset
-        const uint32_t dst = be32_at(h + 16);
-        if (host != 0 && dst != host) return it;
-        if (h[9] != kProtoUdp) return it;
-        const uint32_t l4_len = ip_len - hdr_len;             // the trim to the IP total length
+        if (!status_passes(status[i], need, reject)) return it;
+        wire::Ipv4View ip;
+        if (!wire::ipv4_view(bytes, bytes_len, o, l, &ip)) return it;
+        if ((ip.frag & 0x3FFFu) != 0) return it;              // MF or a fragment offset
+        if (host != 0 && ip.dst() != host) return it;
+        if (ip.proto() != kProtoUdp) return it;
+        const uint32_t l4_len = ip.ip_len - ip.hdr_len;       // the trim to the IP total length
         if (l4_len < kUdpHdr) {
             it.cls = SCCSUM_UDP_SHORT;
             return it;
         }
-        const uint8_t* const u = h + hdr_len;
+        const uint8_t* const u = ip.h + ip.hdr_len;
         it.cls = channel_of(table, be16_at(u + 2));
         if (it.cls >= kMaxChannels) return it;
-        it.add = hdr_len + kUdpHdr;
+        it.add = ip.hdr_len + kUdpHdr;
         it.pay_len = l4_len - kUdpHdr;                         // udp_hdr::len is not consulted
-        it.src = be32_at(h + 12);
+        it.src = ip.src();
         it.sport = be16_at(u);
         return it;
     }
@@ -183,10 +164,7 @@ struct ReasmDecode {
 
     __device__ __forceinline__ Item operator()(uint64_t d) const {
         Item it{SCCSUM_UDP_SKIP, static_cast<uint32_t>(d), 0, 0, 0, 0};
-        if (l4_status) {
-            const uint32_t st = l4_status[d];
-            if ((st & need) != need || (st & reject) != 0) return it;
-        }
+        if (l4_status && !status_passes(l4_status[d], need, reject)) return it;
         const uint64_t hi = head[d];
         if (hi >= nrec) return it;
         const uint64_t* const w = reinterpret_cast<const uint64_t*>(rec + hi);
@@ -238,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void count_kernel(Decode dec, uint32_t chan
                                                        uint4* __restrict__ stash, uint32_t* __restrict__ ws,
                                                        uint32_t pitch) {
     __shared__ uint32_t hist[kMaxBuckets];
-    if (threadIdx.x < kMaxBuckets) hist[threadIdx.x] = 0;
+    bucket_pass::hist_clear(hist);
     __syncthreads();
     const uint64_t j = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = j < dec.n;
@@ -249,54 +227,10 @@ __global__ __launch_bounds__(kBlock) void count_kernel(Decode dec, uint32_t chan
     }
     const uint32_t c = it.cls;
     const uint32_t b = c < channels ? c : channels;
-    const uint64_t m = match_bucket(b, valid);
-    // one LDS add per distinct bucket of the wave: only a count comes out
-    if (valid && (m & lanes_below()) == 0) atomicAdd(&hist[b], static_cast<uint32_t>(__popcll(m)));
+    bucket_pass::hist_add(hist, b, valid);
     if (valid && d_class) d_class[j] = static_cast<uint8_t>(c);
     __syncthreads();
-    if (threadIdx.x <= channels) ws[uint64_t(threadIdx.x) * pitch + blockIdx.x] = hist[threadIdx.x];
-}
-
-// One wave: the bucket totals scanned into d_first (buckets + 1 entries).
-__device__ __forceinline__ void scan_totals(const uint32_t* total, uint32_t buckets, uint32_t* __restrict__ d_first) {
-    const uint32_t lane = lane_id();
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < buckets; base += kWave) {
-        const uint32_t b = base + lane;
-        const uint32_t c = b < buckets ? total[b] : 0u;
-        const uint32_t incl = wave_inclusive_scan(c);
-        if (b < buckets) d_first[b] = carry + incl - c;
-        carry += __shfl(incl, kWave - 1, kWave);
-    }
-    if (lane == 0) d_first[buckets] = carry;
-}
-
-// Few buckets (at most kScanOneBlockMax), or no tile at all: ONE block does
-// both, wave w taking the rows of buckets w, w + 16, ...
-__global__ __launch_bounds__(kBlock) void scan_kernel(uint32_t* __restrict__ ws, uint32_t ntiles, uint32_t pitch,
-                                                      uint32_t buckets, uint32_t* __restrict__ d_first) {
-    __shared__ uint32_t total[kMaxBuckets];
-    const uint32_t wave = threadIdx.x / kWave;
-    for (uint32_t b = wave; b < buckets; b += kWaves) {
-        const uint32_t sum = scan_row(ws, b, ntiles, pitch);
-        if (lane_id() == 0) total[b] = sum;
-    }
-    __syncthreads();
-    if (wave == 0) scan_totals(total, buckets, d_first);
-}
-
-// Many buckets: one wave per bucket scans its row and leaves the total behind
-// the rows, a second launch of one wave scans the totals — the rows are spread
-// over the device, as steer.hip spreads its 256.
-__global__ __launch_bounds__(kWave) void scan_rows_kernel(uint32_t* __restrict__ ws, uint32_t ntiles, uint32_t pitch,
-                                                          uint32_t* __restrict__ totals) {
-    const uint32_t sum = scan_row(ws, blockIdx.x, ntiles, pitch);
-    if (lane_id() == 0) totals[blockIdx.x] = sum;
-}
-
-__global__ __launch_bounds__(kWave) void scan_totals_kernel(const uint32_t* __restrict__ totals, uint32_t buckets,
-                                                            uint32_t* __restrict__ d_first) {
-    scan_totals(totals, buckets, d_first);
+    bucket_pass::hist_store(hist, channels + 1u, ws, pitch);
 }
 
 struct RxOut {
@@ -311,13 +245,11 @@ template <typename Decode>
 __global__ __launch_bounds__(kBlock) void scatter_kernel(Decode dec, uint32_t channels, const uint4* __restrict__ stash,
                                                          const uint32_t* __restrict__ ws, uint32_t pitch,
                                                          const uint32_t* __restrict__ d_first, RxOut O) {
-    // cnt[wave][bucket]: items of the bucket in the wave, then their offset inside the tile;
     // base[bucket]: where the tile's items of the bucket start in the grouped arrays
-    __shared__ uint32_t cnt[kWaves][kMaxBuckets];
     __shared__ uint32_t base[kMaxBuckets];
-    const uint32_t wave = threadIdx.x / kWave;
-    for (uint32_t k = threadIdx.x; k < kWaves * kMaxBuckets; k += kBlock) (&cnt[0][0])[k] = 0;
-    if (threadIdx.x <= channels) base[threadIdx.x] = d_first[threadIdx.x] + ws[uint64_t(threadIdx.x) * pitch + blockIdx.x];
+    bucket_pass::TileRank<kWaves, 1, kMaxBuckets> rank;
+    rank.clear(channels + 1u);
+    bucket_pass::bucket_base(base, channels + 1u, d_first, ws, pitch);
     __syncthreads();
     const uint64_t j = uint64_t(blockIdx.x) * kTile + threadIdx.x;
     const bool valid = j < dec.n;
@@ -325,22 +257,12 @@ __global__ __launch_bounds__(kBlock) void scatter_kernel(Decode dec, uint32_t ch
     if (valid) it = stash[j];
     const uint32_t cls = it.z & 0xFFu;
     const uint32_t b = cls < channels ? cls : channels;
-    const uint64_t m = match_bucket(b, valid);
-    const uint32_t rank = static_cast<uint32_t>(__popcll(m & lanes_below()));
-    if (valid && rank == 0) cnt[wave][b] = static_cast<uint32_t>(__popcll(m));
+    rank.mark(0, b, valid);
     __syncthreads();
-    if (threadIdx.x <= channels) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const uint32_t k = cnt[w][threadIdx.x];
-            cnt[w][threadIdx.x] = run;
-            run += k;
-        }
-    }
+    rank.scan(channels + 1u);
     __syncthreads();
     if (!valid) return;
-    const uint64_t pos = uint64_t(base[b]) + cnt[wave][b] + rank;
+    const uint64_t pos = uint64_t(base[b]) + rank.offset(0, b);
     if (pos >= dec.n) return;  // never for consistent inputs
     O.order[pos] = it.w;
     if (O.pay_off) O.pay_off[pos] = dec.base(it.w) + (it.z >> 8);
@@ -418,15 +340,6 @@ __global__ __launch_bounds__(kSendBlock) void send_kernel(Send S, SendOut O) {
 
 // ---------------------------------------------------------------- host side
 
-// The launches run on the stream's device, which must be `want` (the port
-// table's device), or with want < 0 the calling thread's current one.
-int stream_ok(hipStream_t st, int want) {
-    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
-    const hipError_t e = host_launch::stream_devices(st, &dev, &sd);
-    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
-    return sd != (want < 0 ? dev : want) ? SCCSUM_EINVAL : SCCSUM_OK;
-}
-
 }  // namespace udp
 
 struct sccsum_udp_ports {
@@ -459,7 +372,7 @@ int new_ports(const uint16_t* ports, uint32_t channels, sccsum_udp_ports** out) 
 }
 
 uint64_t rx_workspace(uint64_t n) {
-    const uint64_t pitch = (tiles_of(n) + 3) & ~uint64_t(3);
+    const uint64_t pitch = pitch_of(tiles_of(n, kTile));
     // one 16-byte stash per item, the per-tile counts [253][pitch], then the bucket totals
     return 16u * n + (kMaxBuckets * pitch + kTotals) * 4u;
 }
@@ -468,8 +381,8 @@ uint64_t rx_workspace(uint64_t n) {
 template <typename Decode>
 int run_rx(const Decode& dec, uint32_t channels, uint8_t* d_class, uint32_t* d_first, const RxOut& O, void* d_workspace,
            hipStream_t st) {
-    const uint32_t ntiles = static_cast<uint32_t>(tiles_of(dec.n));
-    const uint32_t pitch = (ntiles + 3u) & ~3u;
+    const uint32_t ntiles = static_cast<uint32_t>(tiles_of(dec.n, kTile));
+    const uint32_t pitch = pitch_of(ntiles);
     const uint32_t buckets = channels + 1u;
     uint4* const stash = static_cast<uint4*>(d_workspace);
     uint32_t* const ws = reinterpret_cast<uint32_t*>(stash + dec.n);
@@ -479,16 +392,8 @@ int run_rx(const Decode& dec, uint32_t channels, uint8_t* d_class, uint32_t* d_f
                           pitch);
         if (e != hipSuccess) return static_cast<int>(e);
     }
-    if (buckets <= kScanOneBlockMax || ntiles == 0) {
-        e = launch_kernel(scan_kernel, dim3(1), dim3(kBlock), 0, st, ws, ntiles, pitch, buckets, d_first);
-    } else {
-        uint32_t* const totals = ws + uint64_t(kMaxBuckets) * pitch;
-        e = launch_kernel(scan_rows_kernel, dim3(buckets), dim3(kWave), 0, st, ws, ntiles, pitch, totals);
-        if (e == hipSuccess) {
-            e = launch_kernel(scan_totals_kernel, dim3(1), dim3(kWave), 0, st, static_cast<const uint32_t*>(totals),
-                              buckets, d_first);
-        }
-    }
+    e = bucket_pass::scan_buckets<kBlock, kMaxBuckets>(st, ws, ntiles, pitch, buckets, d_first,
+                                                       ws + uint64_t(kMaxBuckets) * pitch);
     if (e != hipSuccess || !ntiles) return static_cast<int>(e);
     e = launch_kernel(scatter_kernel<Decode>, dim3(ntiles), dim3(kBlock), 0, st, dec, channels,
                       static_cast<const uint4*>(stash), static_cast<const uint32_t*>(ws), pitch,

@@ -51,8 +51,9 @@ def _guards_intact(t, numel: int, fill: int) -> bool:
 
 
 def _run_and_check(dev, steer, m, h, st=None, need=0, reject=0, mode=HASH2CPU, src=0, want_cpu=True, want_order=True,
-                   msg=""):
-    """One run into guarded outputs, compared with the restatement; returns the host copies."""
+                   msg="", ws_after=None):
+    """One run into guarded outputs, compared with the restatement; returns the host copies.
+    A list given as `ws_after` gets the workspace's bytes as the run left them."""
     n = int(h.size)
     ncpu = m["ncpu"]
     d_h = torch.from_numpy(h.view(np.int32).copy()).to(dev)
@@ -73,6 +74,8 @@ def _run_and_check(dev, steer, m, h, st=None, need=0, reject=0, mode=HASH2CPU, s
     assert int(got_first[-1]) == n
     assert _guards_intact(first_all, ncpu + 2, -7), msg
     assert _guards_intact(ws_all, wsb, 0x5A), msg
+    if ws_after is not None:
+        ws_after.append(ws.cpu().numpy())
     got_cpu = got_order = None
     if want_cpu:
         got_cpu = g_cpu.cpu().numpy()
@@ -149,6 +152,34 @@ def test_either_side_of_the_one_block_scan(dev, ncpu):
     for n in (1, 3 * _tile() + 17):
         _run_and_check(dev, s, m, rand_hashes(rng, n), _status(rng, n), NEED, REJECT)
     _run_and_check(dev, s, m, rand_hashes(rng, 0))
+    s.close()
+
+
+@pytest.mark.parametrize("ncpu", [1, 31, 32, 255])
+@pytest.mark.parametrize("n", [2047, 2048, 2049])
+def test_tile_edge_on_either_scan_path(dev, ncpu, n):
+    """One packet short of a tile, a whole tile, one packet into the second,
+    with and without a status array, at 1, 31, 32 and 255 shards.  32 buckets
+    (31 shards + the dropped) is the last case of the one-block scan, 33 the
+    first that takes a block per bucket and a launch for the totals; that
+    path leaves the bucket totals behind the workspace's rows of per-tile
+    counts and the one-block scan leaves those bytes alone, which pins the
+    switch."""
+    assert _tile() == 2048
+    rng = np.random.default_rng(1000 * ncpu + n)
+    m = random_map(rng, ncpu, 3, 0, 5, unset=False)
+    s = make_steer(m)
+    tiles = -(-n // _tile())
+    at = 4 * (ncpu + 1) * ((tiles + 3) & ~3)  # the rows [ncpu + 1][pitch] of 32-bit counts
+    for st in (_status(rng, n), None):
+        ws = []
+        _, _, first = _run_and_check(dev, s, m, rand_hashes(rng, n), st, NEED if st is not None else 0,
+                                     REJECT if st is not None else 0, msg=f"ncpu={ncpu} n={n}", ws_after=ws)
+        behind = ws[0][at:at + 4 * (ncpu + 1)]
+        if ncpu + 1 <= 32:
+            assert np.all(behind == 0x5A)
+        else:
+            assert np.array_equal(behind.view(np.uint32), np.diff(first))
     s.close()
 
 
