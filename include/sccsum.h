@@ -1697,6 +1697,140 @@ int sccsum_tcp_rx_data(const void* d_bytes, const sccsum_tcp_seg* d_seg, const u
                        const sccsum_tcp_rcv* d_rcv, uint32_t nconns, uint64_t max_bytes, sccsum_tcp_rcv_run* d_run,
                        sccsum_gather_desc* d_desc, uint64_t* d_total, void* d_workspace, void* stream);
 
+/* ---- TCP transmit fast path: every polled connection's unsent queue cut into segments ----
+ * The tx recipe of sccsum_tcp_send starts from payloads and one sccsum_tcp_out
+ * per segment: the host has cut every segment and written its seq.  That cut is
+ * tcb::get_packet's continuation (include/seastar/net/tcp.hh:2089-2111) calling
+ * can_send() (tcp.hh:515-549), get_transmit_packet() (tcp.hh:1578-1606) and
+ * output_one()'s sequence bookkeeping (tcp.hh:1635-1645) once per segment.  For a
+ * tcb in ESTABLISHED or CLOSE_WAIT (ACK on, no SYN, no FIN: tcp.hh:631-640) with
+ * _snd.dupacks == 0, _snd.window_probe false and an empty _packetq the whole
+ * chain is a closed form of the state and the queue's length, and
+ * sccsum_tcp_tx_data evaluates it for a batch: one record per connection going
+ * in, one per connection and one per segment coming out.  Every other tcb
+ * (dupacks 1 or 2: limited transmit, which mutates _snd.limited_transfer;
+ * dupacks >= 3; window probes; SYN and closing states) is left untouched for the
+ * host's own walk, so no outcome depends on the device.
+ *
+ * d_snd[nconns] (48 bytes each, 16-byte aligned), one per polled connection:
+ *   dst, sport, dport       the foreign address, the local and the foreign port
+ *   next, una, window, cwnd, mss    of _snd (unacknowledged as una)
+ *   rcv_next                _rcv.next
+ *   wnd                     the 16-bit header window, _rcv.window >> _rcv.window_scale
+ *   flags                   SCCSUM_TCP_SND_ELIGIBLE: set by the host only under the
+ *                           four conditions above; _RTX_ARMED: _retransmit.armed()
+ * The unsent queues as a CSR: connection c's buffers are j in [d_buf_first[c],
+ * d_buf_first[c + 1]) (nconns + 1 non-decreasing entries from 0 to at most nbuf),
+ * buffer j the d_buf_len[j] bytes at the 64-bit address d_buf_src[j] (device
+ * memory, or pinned / registered host memory, as sccsum_gather takes; never read
+ * here).  A buffer of no bytes contributes no descriptor (the reference appends
+ * an empty fragment, which changes nothing on the wire).  U, _snd.unsent_len, is
+ * the 64-bit sum of the connection's lengths; a queue of more than 2^32 - 1 bytes
+ * is not taken (stop = _STOP_QUEUE: the reference's uint32_t would have wrapped).
+ * opts: src_host (what the same connection's sccsum_tcp_opts carries; not
+ * consulted: no output holds the source address), mtu 68..65535, max_packet_len
+ * 41..65535 (read only with SCCSUM_TCP_TSO), headroom 20..65535, flags:
+ * SCCSUM_TCP_TSO alone.
+ *
+ * The rule, for an eligible connection, with used = uint32(next - una) and
+ * L = TSO ? max_packet_len - 40 : min(uint16(mtu - 40), mss):
+ *   T = (window == 0 || used > window) ? 0 : min(window - used, U)
+ *   P = min(cwnd, L)          can_send() limits every call by cwnd, not by the
+ *                             flight size: the reference's behaviour, reproduced
+ *   T == 0 or P == 0: ONE segment of length 0 (get_packet calls output_one()
+ *     unconditionally first: the pure ACK an output() exists to send), bytes = 0
+ *   otherwise ceil(T / P) segments, segment k with seq = next + k P (mod 2^32) and
+ *     len = min(P, T - k P), its bytes the stream bytes [k P, k P + len) of the
+ *     concatenated buffers whatever their boundaries (whole buffers while they
+ *     fit, then share(0, rest)); bytes = T
+ * With P == 0 through mss == 0 (and cwnd > 0, T > 0) the reference's chain does
+ * not end: can_send() stays positive and every poll sends another empty segment.
+ * The call sends the one; a host should not mark such a tcb eligible.
+ *
+ * d_run[nconns] (32 bytes each, 16-byte aligned): segs; bytes (what the host pops
+ * from its queue); seg_first, the exclusive scan of segs; next after them; flags:
+ * _RTX_ARM, arm the retransmit timer now: not armed on entry and a segment with
+ * len > 0 was emitted (tcp.hh:1700-1710); stop:
+ *   _STOP_END         bytes == U: the queue is exhausted
+ *   _STOP_WINDOW      bytes < U: the window, or segments of no bytes
+ *   _STOP_INELIGIBLE  segs = 0, the state as given
+ *   _STOP_QUEUE       the same, for a queue past 2^32 - 1 bytes
+ *   _STOP_CAPACITY    below
+ * Per segment f of the F emitted, in connection order then stream order, exactly
+ * what sccsum_tcp_send takes: d_off[f] (u64) and d_len[f], the payload's place in
+ * a PACKED staging layout (every segment `headroom` free bytes, then its len
+ * bytes, back to back from 0); d_out[f], a complete sccsum_tcp_out {dst, seq,
+ * ack = rcv_next, sport, dport, window = wnd, flags = 0x10 (f_psh and f_urg are
+ * false, tcp.hh:1632-1633), hdr_len = 20 (tcp_option::get_size(false, true) is
+ * 0), mss}.  d_seg_first[F + 1] and d_desc: one sccsum_gather_desc {buffer
+ * address + inner offset, place in the layout, length} per (segment, buffer)
+ * overlap, segment f's at [d_seg_first[f], d_seg_first[f + 1]), so
+ * sccsum_gather(d_desc, d_total[2], staging) materialises every payload and the
+ * same records tile the segments for sccsum_spans_desc.  Every emitted segment is
+ * one unacked_segment of _snd.data; the staging copy plays the part of its clone,
+ * so the application's buffers are free once the gather has run.  Pieces are at
+ * most F + nbuf: d_desc has room for max_segs + nbuf records; d_off, d_len, d_out
+ * for max_segs, d_seg_first for max_segs + 1.
+ * d_total[4] = {segments emitted, layout bytes emitted, descriptors emitted, the
+ * layout bytes needed without the caps (a connection counts as at most 2^43)}.
+ * Capacity (sccsum_ipv4_send's prefix rule): connections are taken in order while
+ * the segments of connections 0..c are <= max_segs (<= 2^31 - 1) and their layout
+ * bytes <= max_out_bytes (<= 2^32 - 1).  From the first connection that does not
+ * fit onward segs = 0, stop = _STOP_CAPACITY, seg_first = F and the state is as
+ * given; no per-segment array is written past what was emitted.
+ *
+ * Plain dependent launches on `stream` (two tile / carry / place scans over the
+ * buffers, count / scan / place over the connections, one kernel over the
+ * segments), no allocation, no memset, no atomic, no payload byte moves; two
+ * runs give identical bytes.  d_workspace: sccsum_tcp_tx_data_workspace(nconns,
+ * nbuf) bytes, 16-byte aligned.  No output may overlap another array of the call.
+ * SCCSUM_EINVAL before any device work: NULL opts or values outside the ranges
+ * above, unknown flags; a NULL required pointer (d_total, d_seg_first and the
+ * workspace always; with nconns != 0 d_snd, d_buf_first and d_run, the buffer
+ * arrays unless nbuf == 0, the per-segment arrays unless max_segs == 0);
+ * misalignment (d_snd, d_run and the workspace 16; d_buf_src, d_off, d_desc and
+ * d_total 8; the 32-bit arrays and d_out 4); nconns > SCCSUM_TCP_MAX_CONNS, nbuf >
+ * 2^31, max_segs > 2^31 - 1, max_out_bytes > 2^32 - 1; a stream of another device
+ * than the current one.  nconns == 0 writes d_total (all 0) and d_seg_first[0]
+ * and is SCCSUM_OK.  sccsum_tcp_tx_data_seg_tile() segments make one tile of the
+ * segment kernel, whose grid strides past sccsum_tcp_tx_data_max_blocks(). */
+#define SCCSUM_TCP_SND_ELIGIBLE  0x01u
+#define SCCSUM_TCP_SND_RTX_ARMED 0x02u
+#define SCCSUM_TCP_SND_RTX_ARM   0x04u /* run records only */
+#define SCCSUM_TCP_STOP_QUEUE    8u
+
+typedef struct sccsum_tcp_snd {
+    uint32_t dst, next, una, window;
+    uint32_t cwnd, rcv_next;
+    uint16_t sport, dport, mss, wnd;
+    uint8_t flags; /* SCCSUM_TCP_SND_ELIGIBLE | _RTX_ARMED */
+    uint8_t pad[3];
+    uint32_t reserved[3]; /* ignored */
+} sccsum_tcp_snd;
+typedef struct sccsum_tcp_snd_run {
+    uint32_t segs, bytes, seg_first, next;
+    uint8_t flags; /* SCCSUM_TCP_SND_RTX_ARM */
+    uint8_t stop;  /* SCCSUM_TCP_STOP_END, _WINDOW, _INELIGIBLE, _QUEUE, _CAPACITY */
+    uint16_t pad;
+    uint32_t reserved[3]; /* written as 0 */
+} sccsum_tcp_snd_run;
+typedef struct sccsum_tcp_tx_opts {
+    uint32_t src_host;       /* ipv4::_host_address, host order */
+    uint32_t mtu;            /* hw_features().mtu, 68..65535 */
+    uint32_t max_packet_len; /* hw_features().max_packet_len, 41..65535, with SCCSUM_TCP_TSO */
+    uint32_t headroom;       /* 20..65535 */
+    uint32_t flags;          /* SCCSUM_TCP_TSO */
+} sccsum_tcp_tx_opts;
+
+uint64_t sccsum_tcp_tx_data_workspace(uint32_t nconns, uint64_t nbuf);
+int sccsum_tcp_tx_data_seg_tile(void);
+int sccsum_tcp_tx_data_max_blocks(void);
+int sccsum_tcp_tx_data(const sccsum_tcp_tx_opts* opts, const sccsum_tcp_snd* d_snd, uint32_t nconns,
+                       const uint64_t* d_buf_src, const uint32_t* d_buf_len, const uint32_t* d_buf_first, uint64_t nbuf,
+                       uint64_t max_segs, uint64_t max_out_bytes, sccsum_tcp_snd_run* d_run, uint64_t* d_off,
+                       uint32_t* d_len, sccsum_tcp_out* d_out, uint32_t* d_seg_first, sccsum_gather_desc* d_desc,
+                       uint64_t* d_total, void* d_workspace, void* stream);
+
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);
 int sccsum_host_free(void* p);

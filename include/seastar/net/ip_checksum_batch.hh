@@ -1018,6 +1018,62 @@ public:
     }
 };
 
+// TCP tx, the data (<sccsum.h> sccsum_tcp_tx_data): the cut tcb::get_packet's
+// chain makes of every polled connection's unsent queue — can_send(),
+// get_transmit_packet() and output_one's seq (tcp.hh:515-549, 1578-1606,
+// 1635-1645) — for the tcbs on the straight path: one run record per
+// connection, and per segment its place in a packed layout, its sccsum_tcp_out
+// and its gather descriptors, as tcp_tx::run takes them.  No byte moves.
+//   tcp_tx_data cut({host, 1500, 65535, 20, 0});
+//   cut.run(d_snd, nconns, queues, max_segs, max_out_bytes, out, d_ws, stream);
+//   sccsum_gather(out.desc, total[2], d_staging, stream);   // the _snd.data clones: the buffers are free
+//   tx.run(d_staging, total[1], out.off, out.len, out.out, total[0], tx_out, stream);
+class tcp_tx_data {
+    sccsum_tcp_tx_opts _opts;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // the unsent queues as a CSR (device arrays): connection c's buffers are [first[c], first[c + 1])
+    struct queues {
+        const uint64_t* src = nullptr;    // nbuf addresses: device, or pinned / registered host memory
+        const uint32_t* len = nullptr;    // nbuf
+        const uint32_t* first = nullptr;  // nconns + 1
+        uint64_t nbuf = 0;
+    };
+
+    // what run() writes (device arrays; <sccsum.h>, "TCP transmit fast path")
+    struct outputs {
+        sccsum_tcp_snd_run* run = nullptr;   // nconns
+        uint64_t* off = nullptr;             // max_segs
+        uint32_t* len = nullptr;             // max_segs
+        sccsum_tcp_out* out = nullptr;       // max_segs
+        uint32_t* seg_first = nullptr;       // max_segs + 1
+        sccsum_gather_desc* desc = nullptr;  // max_segs + nbuf
+        uint64_t* total = nullptr;           // 4: segments, layout bytes, descriptors emitted; the bytes needed
+    };
+
+    explicit tcp_tx_data(const sccsum_tcp_tx_opts& opts) : _opts(opts) {}
+
+    const sccsum_tcp_tx_opts& opts() const noexcept { return _opts; }
+
+    static uint64_t workspace(uint32_t nconns, uint64_t nbuf) noexcept {
+        return sccsum_tcp_tx_data_workspace(nconns, nbuf);
+    }
+
+    // d_snd: one sccsum_tcp_snd per polled connection, 16-byte aligned; max_segs <= 2^31 - 1, max_out_bytes <= 2^32 - 1
+    void run(const sccsum_tcp_snd* d_snd, uint32_t nconns, const queues& q, uint64_t max_segs, uint64_t max_out_bytes,
+             const outputs& out, void* d_workspace, void* stream) const {
+        check(sccsum_tcp_tx_data(&_opts, d_snd, nconns, q.src, q.len, q.first, q.nbuf, max_segs, max_out_bytes, out.run,
+                                 out.off, out.len, out.out, out.seg_first, out.desc, out.total, d_workspace, stream),
+              "sccsum_tcp_tx_data");
+    }
+};
+
 }  // namespace net
 
 }  // namespace seastar

@@ -2045,6 +2045,156 @@ def tcp_send(payloads: PacketBatch, out: torch.Tensor, src_host: int, mtu: int, 
                          tso_seg=tso[:n], status=status[:n])
 
 
+TCP_SND_DTYPE = np.dtype([("dst", "<u4"), ("next", "<u4"), ("una", "<u4"), ("window", "<u4"), ("cwnd", "<u4"),
+                          ("rcv_next", "<u4"), ("sport", "<u2"), ("dport", "<u2"), ("mss", "<u2"), ("wnd", "<u2"),
+                          ("flags", "u1"), ("pad", "u1", (3,)), ("reserved", "<u4", (3,))])
+TCP_SND_RUN_DTYPE = np.dtype([("segs", "<u4"), ("bytes", "<u4"), ("seg_first", "<u4"), ("next", "<u4"), ("flags", "u1"),
+                              ("stop", "u1"), ("pad", "<u2"), ("reserved", "<u4", (3,))])
+
+
+@dataclass
+class TcpTxDataResult:
+    """What sccsum_tcp_tx_data wrote (include/sccsum.h, "TCP transmit fast
+    path"): every polled connection's unsent queue cut into segments."""
+    run: torch.Tensor          # uint8 [P, 32]: sccsum_tcp_snd_run records (TCP_SND_RUN_DTYPE on the host)
+    off: torch.Tensor          # int64 [max_segs]: the payload's place in the packed layout
+    length: torch.Tensor       # int32 [max_segs]
+    out: torch.Tensor          # uint8 [max_segs, 24]: sccsum_tcp_out records (TCP_OUT_DTYPE on the host)
+    seg_first: torch.Tensor    # int32 [max_segs + 1]: segment f's descriptors are [seg_first[f], seg_first[f + 1])
+    desc: torch.Tensor         # uint8 [16 (max_segs + nbuf)]: one sccsum_gather_desc per (segment, buffer) overlap
+    total: torch.Tensor        # int64 [4]: segments, layout bytes, descriptors emitted; the layout bytes needed
+    max_len: int               # no payload is longer
+    _totals: tuple | None = None
+    _runs: np.ndarray | None = None
+
+    def totals(self) -> tuple:
+        """(segments, layout bytes, descriptors, layout bytes needed) on the host (synchronises once)."""
+        if self._totals is None:
+            self._totals = tuple(int(x) for x in self.total.cpu().numpy().view(np.uint64))
+        return self._totals
+
+    @property
+    def runs(self) -> torch.Tensor:
+        """The P run records (a view)."""
+        return self.run
+
+    def runs_host(self) -> np.ndarray:
+        """The run records on the host as TCP_SND_RUN_DTYPE (synchronises once)."""
+        if self._runs is None:
+            self._runs = self.run.cpu().numpy().reshape(-1).view(TCP_SND_RUN_DTYPE)
+        return self._runs
+
+    @property
+    def descs(self) -> torch.Tensor:
+        """The descriptors emitted, uint8 [pieces, 16] (DESC_DTYPE on the host)."""
+        return self.desc.view(-1, 16)[:self.totals()[2]]
+
+    def pack(self, stream=None) -> tuple:
+        """Gathers every segment's payload into a new staging buffer, behind
+        its headroom, and returns (payloads, out) as tcp_send takes them.  The
+        staging copy is the segments' _snd.data clone: the queues' buffers are
+        free once it has run."""
+        nsegs, nbytes, pieces, _ = self.totals()
+        data = _scratch(_round16(nbytes) or 16, self.desc.device, stream)
+        if pieces:
+            native.check(native.load().sccsum_gather(ctypes_ptr(self.desc), pieces, ctypes_ptr(data), _stream(stream)),
+                         "sccsum_gather")
+        payloads = PacketBatch(data=data, off=self.off[:nsegs], length=self.length[:nsegs], bytes_len=nbytes,
+                               max_len=self.max_len)
+        return payloads, self.out[:nsegs]
+
+    def segs(self, k: int) -> tuple:
+        """Connection k's slice (off, length, out): its new _snd.data entries, in stream order."""
+        r = self.runs_host()[int(k)]
+        lo, hi = int(r["seg_first"]), int(r["seg_first"]) + int(r["segs"])
+        return self.off[lo:hi], self.length[lo:hi], self.out[lo:hi]
+
+
+def tcp_tx_data_check(snd, buf_src, buf_len, buf_first, src_host, mtu, headroom, flags, max_packet_len, max_segs,
+                      max_out_bytes) -> tuple:
+    """What tcp_tx_data refuses before any launch; returns (nconns, nbuf)."""
+    if not isinstance(snd, torch.Tensor) or snd.dim() != 2 or snd.shape[1] != 48:
+        raise ValueError("snd: need a uint8 [nconns, 48] tensor of sccsum_tcp_snd records (TCP_SND_DTYPE)")
+    dev = snd.device
+    nconns = int(snd.shape[0])
+    if nconns > native.TCP_MAX_CONNS:
+        raise ValueError("snd: at most 2^20 connections")
+    _need(snd, 48 * nconns, torch.uint8, "snd", dev)
+    if nconns and snd.data_ptr() % 16:
+        raise ValueError("snd: need a 16-byte aligned tensor")
+    for what, t, dtype in (("buf_src", buf_src, torch.int64), ("buf_len", buf_len, torch.int32),
+                           ("buf_first", buf_first, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D {dtype} tensor")
+        _need(t, t.numel(), dtype, what, dev)
+    nbuf = int(buf_src.numel())
+    if int(buf_len.numel()) != nbuf:
+        raise ValueError("buf_len: need one length per buffer address")
+    if nbuf > native.TCP_TX_MAX_BUFS:
+        raise ValueError("buf_src: at most 2^31 buffers")
+    if int(buf_first.numel()) != nconns + 1:
+        raise ValueError("buf_first: need nconns + 1 entries")
+    if not 68 <= int(mtu) <= 65535:
+        raise ValueError(f"mtu: need 68..65535, got {mtu}")
+    if not 20 <= int(headroom) <= 65535:
+        raise ValueError(f"headroom: need 20..65535, got {headroom}")
+    if int(flags) & ~native.TCP_TSO:
+        raise ValueError(f"flags: unknown bits in {int(flags):#x}")
+    if int(flags) & native.TCP_TSO and not 41 <= int(max_packet_len) <= 65535:
+        raise ValueError(f"max_packet_len: need 41..65535, got {max_packet_len}")
+    if not 0 <= int(src_host) <= 0xFFFFFFFF:
+        raise ValueError("src_host: need a host-order IPv4 address, 0..2^32-1")
+    if not 0 <= int(max_segs) <= native.TCP_TX_MAX_SEGS:
+        raise ValueError("max_segs: need 0..2^31-1")
+    if not 0 <= int(max_out_bytes) <= 0xFFFFFFFF:
+        raise ValueError("max_out_bytes: need 0..2^32-1")
+    return nconns, nbuf
+
+
+def tcp_tx_data(snd: torch.Tensor, buf_src: torch.Tensor, buf_len: torch.Tensor, buf_first: torch.Tensor,
+                src_host: int, mtu: int, max_segs: int, max_out_bytes: int = 0xFFFFFFFF, headroom: int = 20,
+                flags: int = 0, max_packet_len: int = 65535, stream=None) -> TcpTxDataResult:
+    """sccsum_tcp_tx_data: the cut tcb::get_packet's chain makes of every
+    polled connection's unsent queue (can_send, get_transmit_packet and
+    output_one's seq, tcp.hh:515-549, 1578-1606, 1635-1645), for the tcbs on
+    the straight path; the others come back untouched (TCP_STOP_INELIGIBLE).
+
+        d = tcp_tx_data(snd, src, length, first, me, 1500, max_segs=1 << 16)   # snd: TCP_SND_DTYPE as uint8 [P, 48]
+        payloads, out = d.pack()                       # the staging copy: the queues' buffers are free
+        t = tcp_send(payloads, out, me, 1500)          # and on as tcp_send's recipe goes
+        for k, run in enumerate(d.runs_host()):        # one record per connection: pop run.bytes, next, the timer
+            ...                                        # d.segs(k): its new _snd.data entries
+
+    Connections are taken while their segments fit max_segs and their layout
+    bytes max_out_bytes; from the first that does not fit onward they take
+    nothing (stop = TCP_STOP_CAPACITY)."""
+    lib = native.load()
+    nconns, nbuf = tcp_tx_data_check(snd, buf_src, buf_len, buf_first, src_host, mtu, headroom, flags, max_packet_len,
+                                     max_segs, max_out_bytes)
+    dev = snd.device
+    k = max(int(max_segs), 1)
+    run = _scratch(4 * max(nconns, 1), dev, stream, torch.int64)
+    off = _scratch(k, dev, stream, torch.int64)
+    length = _scratch(k, dev, stream, torch.int32)
+    out = _scratch(3 * k, dev, stream, torch.int64)
+    seg_first = _scratch(k + 1, dev, stream, torch.int32)
+    desc = _scratch(2 * (k + nbuf), dev, stream, torch.int64)
+    total = _scratch(4, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_tcp_tx_data_workspace(nconns, nbuf)), dev, stream)
+    opts = native.TcpTxOpts(int(src_host), int(mtu), int(max_packet_len), int(headroom), int(flags))
+    code = lib.sccsum_tcp_tx_data(
+        ctypes.addressof(opts), ctypes_ptr(snd) if nconns else None, nconns, ctypes_ptr(buf_src) if nbuf else None,
+        ctypes_ptr(buf_len) if nbuf else None, ctypes_ptr(buf_first), nbuf, int(max_segs), int(max_out_bytes),
+        ctypes_ptr(run), ctypes_ptr(off), ctypes_ptr(length), ctypes_ptr(out), ctypes_ptr(seg_first), ctypes_ptr(desc),
+        ctypes_ptr(total), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_tcp_tx_data")
+    bound = int(max_packet_len) - 40 if int(flags) & native.TCP_TSO else int(mtu) - 40
+    return TcpTxDataResult(run=run.view(torch.uint8).view(-1, 32)[:nconns], off=off[:int(max_segs)],
+                           length=length[:int(max_segs)], out=out.view(torch.uint8).view(-1, 24)[:int(max_segs)],
+                           seg_first=seg_first[:int(max_segs) + 1],
+                           desc=desc.view(torch.uint8)[:16 * (int(max_segs) + nbuf)], total=total, max_len=bound)
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

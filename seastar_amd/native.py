@@ -179,6 +179,11 @@ _PROTOS = {
     "sccsum_tcp_rx_data_workspace": (_u64, [_u64, _u32]),
     "sccsum_tcp_rx_data": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _u64, _vp, _vp, _vp, _vp,
                                           _vp]),
+    "sccsum_tcp_tx_data_workspace": (_u64, [_u32, _u64]),
+    "sccsum_tcp_tx_data_seg_tile": (ctypes.c_int, []),
+    "sccsum_tcp_tx_data_max_blocks": (ctypes.c_int, []),
+    "sccsum_tcp_tx_data": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -342,6 +347,20 @@ class TcpOut(ctypes.Structure):
 class TcpOpts(ctypes.Structure):
     """sccsum_tcp_opts: what output_one takes from its ipv4 (source address, MTU, offload flags)."""
     _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+TCP_SND_ELIGIBLE = 0x01     # sccsum_tcp_snd.flags: the tcb's transmit chain is the closed form
+TCP_SND_RTX_ARMED = 0x02    # _retransmit.armed()
+TCP_SND_RTX_ARM = 0x04      # sccsum_tcp_snd_run.flags: arm the retransmit timer now
+TCP_STOP_QUEUE = 8          # sccsum_tcp_snd_run.stop: a queue of more than 2^32 - 1 bytes
+TCP_TX_MAX_BUFS = 1 << 31
+TCP_TX_MAX_SEGS = 0x7FFFFFFF
+
+
+class TcpTxOpts(ctypes.Structure):
+    """sccsum_tcp_tx_opts: what get_transmit_packet takes from hw_features(), and the layout's headroom."""
+    _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("max_packet_len", ctypes.c_uint32),
+                ("headroom", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class Fragment(ctypes.Structure):
