@@ -65,10 +65,11 @@ class Wires:
         raise AssertionError(f"address {addr:#x} lies in no wire buffer")
 
 
-def run_rx(dev, steer, batches, tables, host_address=HOST) -> tuple:
+def run_rx(dev, steer, batches, tables, host_address=HOST, wires=None) -> tuple:
     """The rx recipe, batch after batch, exactly as INTEGRATION.md writes it.
-    Returns (per batch a dict of host arrays, the Wires)."""
-    wires = Wires(dev)
+    Returns (per batch a dict of host arrays, the Wires).  wires: a Wires whose
+    add() lays the frames out elsewhere (tests/test_gpu_wide_stack.py)."""
+    wires = Wires(dev) if wires is None else wires
     carry = torch.zeros(0, dtype=torch.uint8, device=dev)
     outs = []
     for b, frames in enumerate(batches):
@@ -93,6 +94,7 @@ def run_rx(dev, steer, batches, tables, host_address=HOST) -> tuple:
         outs.append(dict(
             bounds=rx.bounds(), idx=[rx.indices(j).cpu().numpy().view(np.uint32) for j in range(3)],
             cls=rx.cls.cpu().numpy(), mac=[rx.src_mac(j).cpu().numpy().view(np.uint64) for j in range(3)],
+            ip_off=ip.off.cpu().numpy().view(np.uint64),
             status=status.cpu().numpy(), hashes=_u32(hashes), learn=learn.cpu().numpy().view(batch.ARP_REC_DTYPE),
             records=records.cpu().numpy().view(batch.REC_DTYPE), totals=(d, k, npend, nhost),
             dgram_first=_u32(first), dgram_off=off.cpu().numpy().view(np.uint64), dgram_len=_u32(length),

@@ -25,9 +25,14 @@ The checker is the oracle on a compact host image (the same bytes at small
 host offsets; the multi-GiB spans on the module's one host copy of the
 buffer).  Every packet of every case is compared.
 
-Not covered: a buffer crossing a 64 GiB-aligned address (the wrap of the
-16-byte unit index the flat kernel re-bases its buffer resources with); a test
-cannot choose where an allocation lands.  Host pipelines and burst queues over
+The stack layers that came later (steer, ipv4_send, reassembly, Ethernet,
+UDP, TCP, tcp_rx_data, tcp_tx_data) see frames at such offsets in
+tests/test_gpu_wide_stack.py, laid out by tests/wide_layout.py.
+
+Not covered, here or there: a buffer crossing a 64 GiB-aligned address (the
+wrap of the 16-byte unit index the flat kernel re-bases its buffer resources
+with); a test cannot choose where an allocation lands.  A packed output of
+more than 4 GiB: dst_off is 32-bit by contract.  Host pipelines and burst queues over
 more than 4 GiB of host memory are out of scope (their offset checks are in
 part A; burst batches are 32-bit by contract).
 """
