@@ -1831,6 +1831,151 @@ int sccsum_tcp_tx_data(const sccsum_tcp_tx_opts* opts, const sccsum_tcp_snd* d_s
                        uint32_t* d_len, sccsum_tcp_out* d_out, uint32_t* d_seg_first, sccsum_gather_desc* d_desc,
                        uint64_t* d_total, void* d_workspace, void* stream);
 
+/* ---- TCP ACK fast path: the advancing pure ACKs of every connection's run ---------------
+ * The sender half of header prediction for a batch.  A bulk sender's inbound
+ * traffic is pure ACKs that advance SND.UNA; sccsum_tcp_rx_data refuses every one
+ * (_STOP_EMPTY, _STOP_ACK).  Of tcb::input_handle_other_state (include/seastar/
+ * net/tcp.hh:1215-1575) such a segment takes only the advancing-ACK branch
+ * (tcp.hh:1336-1400 with dupacks < 3): data_segment_acked (tcp.hh:1026-1055) with
+ * update_rto (tcp.hh:2016-2039) and update_cwnd (tcp.hh:2042-2052), the window
+ * update (tcp.hh:1316-1329, 1341-1343), the retransmit timer, and the closing
+ * can_send() / output() (tcp.hh:1570-1574).
+ *
+ * sccsum_tcp_rx_acks takes the leading stretch of such ACKs of every run of
+ * sccsum_tcp_rx's bucket 0 and leaves the host one record per run holding all it
+ * applies to the tcb; the next sccsum_tcp_snd record follows from it without
+ * touching a segment.  What is not taken, d_seg[d_run_first[r] + taken ..
+ * d_run_first[r + 1]), reaches the host whole and in order, to be walked with the
+ * real tcb from the state in the record: every stop is conservative and no
+ * outcome depends on the device.
+ *
+ * Inputs: d_seg, d_first, d_run_conn, d_run_first, d_rx_total and n exactly as
+ * sccsum_tcp_rx_data takes them (no host synchronisation, capturable).  No payload
+ * byte is read.  d_ack[nconns] (64 bytes each, 16-byte aligned), indexed by
+ * connection index, is the host's view of each tcb:
+ *   una, next, window, wl1, wl2, cwnd, ssthresh, unsent_len   the _snd fields
+ *                  (unacknowledged as una) as they stand
+ *   rcv_next       _rcv.next
+ *   rto            _rto in ms; srtt, rttvar: _snd.srtt, _snd.rttvar in ms (int64)
+ *   mss            _snd.mss; window_scale: _snd.window_scale
+ *   flags          SCCSUM_TCP_ACK_ELIGIBLE: set by the host only for a tcb in
+ *                  ESTABLISHED or CLOSE_WAIT with _snd.dupacks < 3, _snd.window_probe
+ *                  false, zero_window_probing_out == 0, _snd.window != 0 and
+ *                  window_scale <= 14; _CLOSE_WAIT: the state is CLOSE_WAIT (there
+ *                  tcp.hh:1522-1526 returns before the closing output());
+ *                  _FIRST_SAMPLE: _snd.first_rto_sample
+ *   reserved       ignored
+ * The retransmit queues (_snd.data) as a CSR, as sccsum_tcp_tx_data takes its
+ * buffers: connection c's entries are j in [d_q_first[c], d_q_first[c + 1])
+ * (nconns + 1 entries, read as clamped into [0, nq] and non-decreasing);
+ * d_q_len[j] the entry's current p.len(); d_q_meta[j] = data_len | (nr_transmits
+ * != 0) << 16; d_q_tx[j] (int64) its tx_time in nanoseconds of the clock of
+ * now_ns, the one clock_type::now() of the batch (lowres_clock does not move
+ * inside one poll).
+ *
+ * The device treats a connection as _STOP_INELIGIBLE when ELIGIBLE is clear, conn
+ * >= nconns, window == 0, cwnd == 0 (update_cwnd would divide by it), cwnd >=
+ * 2^31, window_scale > 14 or int32(next - una) < 0; as _STOP_QUEUE when the 64-bit
+ * sum of its entries' lengths is not uint32(next - una) or any entry has length
+ * 0 (the reference holds none: tcp.hh:1702-1706 pushes only len > 0 and a partial
+ * ACK trims strictly inside an entry).
+ *
+ * The rule.  Sequence numbers compare as tcp_seq does: a < b iff int32(a - b) <
+ * 0 (tcp.hh:220-226).  For run r of connection c let prev be una for the run's
+ * first segment and the previous segment's ack otherwise.  Segment i is taken
+ * iff every earlier one was and none of these holds, tested in this order; the
+ * first that holds is the run's `stop`:
+ *   _STOP_INELIGIBLE, _STOP_QUEUE   above
+ *   _STOP_SEQ      seq != rcv_next                      (tcp.hh:1058-1064, 1231-1245)
+ *   _STOP_FLAGS    (flags & 0x37) != 0x10: FIN, SYN, RST or URG, or no ACK
+ *   _STOP_DATA     pay_len != 0: text is sccsum_tcp_rx_data's business
+ *   _STOP_ACK      not (prev < ack && ack <= next): a duplicate, an old ACK or one
+ *                  beyond SND.NXT                       (tcp.hh:1401-1444)
+ *   _STOP_WL       the run's first segment only: not (wl1 < seq || (wl1 == seq &&
+ *                  wl2 <= ack)) (tcp.hh:1341; after a taken ACK wl1 == seq and wl2
+ *                  == prev < ack, so it can only hold at a head)
+ *   _STOP_WINDOW   (window16 << window_scale) == 0: update_window would arm the
+ *                  persist timer with the _rto of that moment (tcp.hh:1323-1325)
+ *   _STOP_END (0)  the run is exhausted
+ * The effect of the taken ACKs is the reference's loop, literally.  For each in
+ * order: pop queue entries while una + len <= ack, each pop doing una += len,
+ * update_rto(tx_time) unless the entry was retransmitted, update_cwnd(len) and
+ * queue_freed += data_len; then, if una < ack still, partial = ack - una trims
+ * the front entry, una = ack and update_cwnd(partial); then window = window16 <<
+ * window_scale.
+ *   update_cwnd(bytes), uint32:  cwnd < ssthresh ? cwnd += min(bytes, mss)
+ *                                                : cwnd += max(1, mss * mss / cwnd)
+ *   update_rto(tx), int64 with C's truncating division:
+ *     R = (now_ns - tx) / 1000000
+ *     first sample: rttvar = R / 2, srtt = R, _FIRST_SAMPLE cleared; later ones:
+ *     delta = |srtt - R|, rttvar = rttvar * 3 / 4 + delta / 4, srtt = srtt * 7 / 8 + R / 8
+ *     rto = clamp(srtt + max(1, 4 rttvar), 1000, 60000)
+ * can_send() > 0 after taken ACK i is unsent_len > 0 && uint32(next - ack_i) <
+ * window_i (dupacks is 0 after exit_fast_recovery, cwnd only grows from a
+ * positive value, window_i != 0).
+ *
+ * d_run[R] (64 bytes each, 16-byte aligned, room for min(n, nconns)): taken; una
+ * after them; acked = una - una as given; popped, the entries popped; trim, the
+ * bytes trimmed off the new front entry; queue_freed; window; cwnd; srtt, rttvar,
+ * rto; flags: _FIRST_SAMPLE after the taken ACKs; _ALL_ACKED: the queue is empty
+ * (stop the retransmit timer, signal_all_data_acked); _RTX_REARM: taken > 0 and
+ * the queue is not empty (rearm at now + rto); _POLL: _CLOSE_WAIT is clear and
+ * some taken ACK had can_send() > 0 (clear_delayed_ack(); output()); stop;
+ * reserved words written as 0.  With taken == 0 the state fields are as given and
+ * no flag but _FIRST_SAMPLE is set; a run whose conn >= nconns has them 0.
+ * d_total[4] = {R, taken ACKs, popped entries, acked bytes}, 8-byte aligned.
+ *
+ * Plain dependent launches on `stream` (two tile / carry / place scans over the
+ * queue entries, one kernel over the records, one over the runs with one lane per
+ * run, one block for d_total), no allocation, no memset, no atomic; two runs give
+ * identical bytes.  A run's lane walks its taken ACKs and popped entries one at
+ * a time: srtt / rttvar are a truncating integer average that does not compose,
+ * so one connection carrying the whole batch is the slow case.  d_workspace:
+ * sccsum_tcp_rx_acks_workspace(n, nconns, nq) bytes, 16-byte aligned.  No output
+ * may overlap another array of the call.  SCCSUM_EINVAL before any device work: a
+ * NULL required pointer (d_total and the workspace always; d_q_first unless
+ * nconns == 0; with n != 0 every other one, but d_ack only unless nconns == 0 and
+ * d_q_len, d_q_meta, d_q_tx only unless nq == 0), misalignment (d_ack, d_run and
+ * the workspace 16; d_seg, d_q_tx, d_total and d_rx_total 8; the 32-bit arrays
+ * 4), n > 2^32 - 1, nconns > SCCSUM_TCP_MAX_CONNS, nq > 2^31, a stream of another
+ * device than the current one.  n == 0 writes d_total (all 0) and is SCCSUM_OK. */
+#define SCCSUM_TCP_ACK_ELIGIBLE     0x01u
+#define SCCSUM_TCP_ACK_CLOSE_WAIT   0x02u
+#define SCCSUM_TCP_ACK_FIRST_SAMPLE 0x04u /* sccsum_tcp_ack and run records */
+#define SCCSUM_TCP_ACK_ALL_ACKED    0x08u /* run records only, as the next two */
+#define SCCSUM_TCP_ACK_RTX_REARM    0x10u
+#define SCCSUM_TCP_ACK_POLL         0x20u
+#define SCCSUM_TCP_STOP_DATA        9u
+#define SCCSUM_TCP_STOP_WL          10u
+
+typedef struct sccsum_tcp_ack {
+    uint32_t una, next, window, wl1;
+    uint32_t wl2, cwnd, ssthresh, unsent_len;
+    uint32_t rcv_next, rto;
+    int64_t srtt, rttvar;
+    uint16_t mss;
+    uint8_t window_scale;
+    uint8_t flags; /* SCCSUM_TCP_ACK_ELIGIBLE | _CLOSE_WAIT | _FIRST_SAMPLE */
+    uint32_t reserved; /* ignored */
+} sccsum_tcp_ack;
+typedef struct sccsum_tcp_ack_run {
+    uint32_t taken, una, acked, popped;
+    uint32_t trim, queue_freed, window, cwnd;
+    int64_t srtt, rttvar;
+    uint32_t rto;
+    uint8_t flags; /* SCCSUM_TCP_ACK_FIRST_SAMPLE | _ALL_ACKED | _RTX_REARM | _POLL */
+    uint8_t stop;  /* SCCSUM_TCP_STOP_* */
+    uint16_t pad;
+    uint32_t reserved[2]; /* written as 0 */
+} sccsum_tcp_ack_run;
+
+uint64_t sccsum_tcp_rx_acks_workspace(uint64_t n, uint32_t nconns, uint64_t nq);
+int sccsum_tcp_rx_acks(const sccsum_tcp_seg* d_seg, const uint32_t* d_first, const uint32_t* d_run_conn,
+                       const uint32_t* d_run_first, const uint64_t* d_rx_total, uint64_t n, const sccsum_tcp_ack* d_ack,
+                       uint32_t nconns, const uint32_t* d_q_first, const uint32_t* d_q_len, const uint32_t* d_q_meta,
+                       const int64_t* d_q_tx, uint64_t nq, int64_t now_ns, sccsum_tcp_ack_run* d_run, uint64_t* d_total,
+                       void* d_workspace, void* stream);
+
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);
 int sccsum_host_free(void* p);

@@ -1074,6 +1074,57 @@ public:
     }
 };
 
+// TCP rx, the ACKs (<sccsum.h> sccsum_tcp_rx_acks): the sender half of header
+// prediction for a batch.  The leading stretch of every run of tcp_rx's bucket
+// 0 that is pure ACKs advancing SND.UNA — the advancing-ACK branch of
+// input_handle_other_state (tcp.hh:1336-1400) with data_segment_acked,
+// update_rto, update_cwnd and the window update, and nothing else — becomes one
+// run record holding all the host applies to the tcb; the rest of a run is the
+// tcb's to walk, from the state in the record.  No payload byte is read.
+//   tcp_rx_acks acks(conns.count());
+//   acks.run(rx_out, n, d_ack, queues, now_ns, out, d_ws, stream);   // rx_out: what tcp_rx::run wrote
+class tcp_rx_acks {
+    uint32_t _nconns;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // the retransmit queues (_snd.data) as a CSR (device arrays): connection c's entries are [first[c], first[c + 1])
+    struct queues {
+        const uint32_t* first = nullptr;  // nconns + 1
+        const uint32_t* len = nullptr;    // nq: the entry's current p.len()
+        const uint32_t* meta = nullptr;   // nq: data_len | (nr_transmits != 0) << 16
+        const int64_t* tx = nullptr;      // nq: tx_time in ns of now_ns's clock
+        uint64_t nq = 0;
+    };
+
+    // what run() writes (device arrays; <sccsum.h>, "TCP ACK fast path")
+    struct outputs {
+        sccsum_tcp_ack_run* run = nullptr;   // min(n, nconns), 16-byte aligned
+        uint64_t* total = nullptr;           // 4: R, taken ACKs, popped entries, acked bytes
+    };
+
+    // nconns: the entries of d_ack, the table's count()
+    explicit tcp_rx_acks(uint32_t nconns) : _nconns(nconns) {}
+
+    uint32_t nconns() const noexcept { return _nconns; }
+
+    uint64_t workspace(uint64_t n, uint64_t nq) const noexcept { return sccsum_tcp_rx_acks_workspace(n, _nconns, nq); }
+
+    // rx, n: tcp_rx::run's outputs as they stand on the device and its n; d_ack: one sccsum_tcp_ack per
+    // connection, 16-byte aligned; now_ns: the one clock_type::now() of the batch
+    void run(const tcp_rx::outputs& rx, uint64_t n, const sccsum_tcp_ack* d_ack, const queues& q, int64_t now_ns,
+             const outputs& out, void* d_workspace, void* stream) const {
+        check(sccsum_tcp_rx_acks(rx.seg, rx.first, rx.run_conn, rx.run_first, rx.total, n, d_ack, _nconns, q.first, q.len,
+                                 q.meta, q.tx, q.nq, now_ns, out.run, out.total, d_workspace, stream),
+              "sccsum_tcp_rx_acks");
+    }
+};
+
 }  // namespace net
 
 }  // namespace seastar

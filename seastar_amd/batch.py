@@ -2195,6 +2195,128 @@ def tcp_tx_data(snd: torch.Tensor, buf_src: torch.Tensor, buf_len: torch.Tensor,
                            desc=desc.view(torch.uint8)[:16 * (int(max_segs) + nbuf)], total=total, max_len=bound)
 
 
+TCP_ACK_DTYPE = np.dtype([("una", "<u4"), ("next", "<u4"), ("window", "<u4"), ("wl1", "<u4"), ("wl2", "<u4"),
+                          ("cwnd", "<u4"), ("ssthresh", "<u4"), ("unsent_len", "<u4"), ("rcv_next", "<u4"),
+                          ("rto", "<u4"), ("srtt", "<i8"), ("rttvar", "<i8"), ("mss", "<u2"), ("window_scale", "u1"),
+                          ("flags", "u1"), ("reserved", "<u4")])
+TCP_ACK_RUN_DTYPE = np.dtype([("taken", "<u4"), ("una", "<u4"), ("acked", "<u4"), ("popped", "<u4"), ("trim", "<u4"),
+                              ("queue_freed", "<u4"), ("window", "<u4"), ("cwnd", "<u4"), ("srtt", "<i8"),
+                              ("rttvar", "<i8"), ("rto", "<u4"), ("flags", "u1"), ("stop", "u1"), ("pad", "<u2"),
+                              ("reserved", "<u4", (2,))])
+
+
+@dataclass
+class TcpAckQueues:
+    """The retransmit queues (_snd.data) of every connection as a CSR:
+    connection c's entries are [first[c], first[c + 1])."""
+    first: torch.Tensor        # int32 [nconns + 1]
+    length: torch.Tensor       # int32 [nq]: the entry's current p.len()
+    meta: torch.Tensor         # int32 [nq]: data_len | (nr_transmits != 0) << 16
+    tx: torch.Tensor           # int64 [nq]: tx_time in ns of now_ns's clock
+
+
+@dataclass
+class TcpRxAcksResult:
+    """What sccsum_tcp_rx_acks wrote (include/sccsum.h, "TCP ACK fast path"):
+    the leading stretch of advancing pure ACKs of every run of tcp_rx's bucket 0."""
+    rx: TcpRxResult
+    run: torch.Tensor          # uint8 [>= R, 64]: sccsum_tcp_ack_run records (TCP_ACK_RUN_DTYPE on the host)
+    total: torch.Tensor        # int64 [4]: R, taken ACKs, popped entries, acked bytes
+    _totals: tuple | None = None
+    _runs: np.ndarray | None = None
+
+    def totals(self) -> tuple:
+        """(R, taken, popped, acked) on the host (synchronises once)."""
+        if self._totals is None:
+            self._totals = tuple(int(x) for x in self.total.cpu().numpy().view(np.uint64))
+        return self._totals
+
+    @property
+    def runs(self) -> torch.Tensor:
+        """The R run records (a view)."""
+        return self.run[:self.rx.totals()[0]]
+
+    def runs_host(self) -> np.ndarray:
+        """The run records on the host as TCP_ACK_RUN_DTYPE (synchronises once)."""
+        if self._runs is None:
+            self._runs = self.runs.cpu().numpy().reshape(-1).view(TCP_ACK_RUN_DTYPE)
+        return self._runs
+
+    def rest(self, conn_run: int) -> torch.Tensor:
+        """The records of run conn_run the host still has to walk with its
+        tcb, from the state in the run record: segs(conn_run)[taken:]."""
+        segs = self.rx.segs(conn_run)
+        return segs[int(self.runs_host()["taken"][int(conn_run)]):]
+
+
+def tcp_rx_acks_check(rx, ack_state, queue, now_ns) -> tuple:
+    """What tcp_rx_acks refuses before any launch; returns (n, nconns, nq)."""
+    if not isinstance(rx, TcpRxResult):
+        raise ValueError("rx: need the TcpRxResult of tcp_rx")
+    dev = rx.seg.device
+    n = int(rx.seg.shape[0])
+    if not isinstance(ack_state, torch.Tensor) or ack_state.dim() != 2 or ack_state.shape[1] != 64:
+        raise ValueError("ack_state: need a uint8 [nconns, 64] tensor of sccsum_tcp_ack records (TCP_ACK_DTYPE)")
+    nconns = int(ack_state.shape[0])
+    if nconns > native.TCP_MAX_CONNS:
+        raise ValueError("ack_state: at most 2^20 connections")
+    _need(ack_state, 64 * nconns, torch.uint8, "ack_state", dev)
+    if nconns and ack_state.data_ptr() % 16:
+        raise ValueError("ack_state: need a 16-byte aligned tensor")
+    if int(rx.run_conn.numel()) < min(n, nconns) + 1:
+        raise ValueError(f"ack_state: {nconns} connections, but rx was made with a table of fewer")
+    if not isinstance(queue, TcpAckQueues):
+        raise ValueError("queue: need a TcpAckQueues")
+    for what, t, dtype in (("queue.first", queue.first, torch.int32), ("queue.length", queue.length, torch.int32),
+                           ("queue.meta", queue.meta, torch.int32), ("queue.tx", queue.tx, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D {dtype} tensor")
+        _need(t, t.numel(), dtype, what, dev)
+    nq = int(queue.length.numel())
+    if nq > native.TCP_ACK_MAX_ENTRIES:
+        raise ValueError("queue.length: at most 2^31 entries")
+    if int(queue.meta.numel()) != nq:
+        raise ValueError("queue.meta: need one word per entry")
+    if int(queue.tx.numel()) != nq:
+        raise ValueError("queue.tx: need one time per entry")
+    if int(queue.first.numel()) != nconns + 1:
+        raise ValueError("queue.first: need nconns + 1 entries")
+    if not -(1 << 63) <= int(now_ns) < (1 << 63):
+        raise ValueError("now_ns: need a signed 64-bit count of nanoseconds")
+    return n, nconns, nq
+
+
+def tcp_rx_acks(rx: TcpRxResult, ack_state: torch.Tensor, queue: TcpAckQueues, now_ns: int,
+                stream=None) -> TcpRxAcksResult:
+    """sccsum_tcp_rx_acks: the sender half of header prediction for a batch —
+    the leading stretch of every connection's run that is pure ACKs advancing
+    SND.UNA: data_segment_acked with update_rto and update_cwnd, the window
+    update and the closing can_send() (tcp.hh:1336-1400, 1026-1055, 1570-1574).
+
+        a = tcp_rx_acks(r, ack_state, queues, now_ns)  # ack_state: TCP_ACK_DTYPE records as uint8 [nconns, 64]
+        for k, run in enumerate(a.runs_host()):        # one record per connection: all the tcb takes over
+            ...                                        # pop run.popped entries, trim run.trim, una, window, cwnd, rto
+            a.rest(k)                                  # what the tcb still walks itself, from that state
+
+    The next tcp_tx_data record (una, window, cwnd) follows from the run
+    record without touching a segment."""
+    lib = native.load()
+    n, nconns, nq = tcp_rx_acks_check(rx, ack_state, queue, now_ns)
+    dev = rx.seg.device
+    run = _scratch(8 * (min(n, nconns) + 1), dev, stream, torch.int64)
+    total = _scratch(4, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_tcp_rx_acks_workspace(n, nconns, nq)), dev, stream)
+    empty = n == 0  # an empty tensor has no address
+    code = lib.sccsum_tcp_rx_acks(
+        None if empty else ctypes_ptr(rx.seg), ctypes_ptr(rx.first), ctypes_ptr(rx.run_conn),
+        ctypes_ptr(rx.run_first), ctypes_ptr(rx.total), n, ctypes_ptr(ack_state) if nconns else None, nconns,
+        ctypes_ptr(queue.first), ctypes_ptr(queue.length) if nq else None, ctypes_ptr(queue.meta) if nq else None,
+        ctypes_ptr(queue.tx) if nq else None, nq, int(now_ns), ctypes_ptr(run), ctypes_ptr(total), ctypes_ptr(ws),
+        _stream(stream))
+    native.check(code, "sccsum_tcp_rx_acks")
+    return TcpRxAcksResult(rx=rx, run=run.view(torch.uint8).view(-1, 64), total=total)
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

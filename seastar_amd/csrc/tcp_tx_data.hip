@@ -20,7 +20,7 @@
 //
 // Plain dependent launches on the caller's stream, no block waiting on another
 // one, no atomic, no payload byte moves:
-//   scan_tile / scan_carry / scan_place   twice over the buffers: the 64-bit
+//   scan_tile / scan_carry / scan_place   (array_scan.h) twice over the buffers: the 64-bit
 //                exclusive scan G of the lengths (a queue's length and a
 //                buffer's stream offset are differences of it), then the 32-bit
 //                scan M of "begins off a segment cut", which needs G
@@ -36,6 +36,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "array_scan.h"
 #include "host_launch.h"
 #include "sccsum.h"
 #include "wave_scan.h"
@@ -43,6 +44,8 @@
 
 namespace tcp_tx_data {
 
+using array_scan::LoadLen;
+using array_scan::scan_array;   // the exclusive scan of an array: tile / carry / place
 using host_launch::launch_kernel;
 using host_launch::misaligned;
 using host_launch::stream_ok;
@@ -69,65 +72,6 @@ static_assert(offsetof(sccsum_tcp_snd, cwnd) == 16 && offsetof(sccsum_tcp_snd, s
                   offsetof(sccsum_tcp_snd, mss) == 28 && offsetof(sccsum_tcp_snd, flags) == 32 &&
                   offsetof(sccsum_tcp_snd_run, flags) == 16 && offsetof(sccsum_tcp_snd_run, stop) == 17,
               "the kernels read and write the records as 16-byte words");
-
-// ---------------------------------------------------------------- the exclusive scan of an array
-
-// Load: V operator()(uint64_t i) const, the item's term; i is below n.
-struct LoadLen {
-    const uint32_t* len;
-    __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return len[i]; }
-};
-
-template <typename V, typename Load>
-__global__ __launch_bounds__(kBlock) void scan_tile(Load L, uint64_t n, V* __restrict__ tsum) {
-    __shared__ V part[kWaves];
-    const uint64_t i = uint64_t(blockIdx.x) * kTile + threadIdx.x;
-    V total;
-    (void)block_inclusive_scan<kWaves>(i < n ? L(i) : V(0), part, &total);
-    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-// ONE block: the tile sums become exclusive prefixes in place; *closing = the sum.
-template <typename V>
-__global__ __launch_bounds__(kBlock) void scan_carry(V* __restrict__ tsum, uint64_t ntiles, V* __restrict__ closing) {
-    __shared__ V part[kWaves];
-    V carry = 0;
-    for (uint64_t base = 0; base < ntiles; base += kBlock) {
-        const uint64_t t = base + threadIdx.x;
-        const V v = t < ntiles ? tsum[t] : V(0);
-        V total;
-        const V incl = carry + block_inclusive_scan<kWaves>(v, part, &total);
-        if (t < ntiles) tsum[t] = incl - v;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *closing = carry;
-}
-
-template <typename V, typename Load>
-__global__ __launch_bounds__(kBlock) void scan_place(Load L, uint64_t n, const V* __restrict__ tsum,
-                                                     V* __restrict__ out) {
-    __shared__ V part[kWaves];
-    const uint64_t i = uint64_t(blockIdx.x) * kTile + threadIdx.x;
-    const V v = i < n ? L(i) : V(0);
-    V total;
-    const V incl = block_inclusive_scan<kWaves>(v, part, &total);
-    if (i < n) out[i] = tsum[blockIdx.x] + incl - v;
-}
-
-// out[0 .. n] = the exclusive scan of L over [0, n) and its sum; `tsum` is one V per tile.
-template <typename V, typename Load>
-hipError_t scan_array(hipStream_t st, const Load& L, uint64_t n, V* tsum, V* out) {
-    const uint64_t ntiles = tiles_of(n, kTile);
-    const dim3 tiles(static_cast<unsigned>(ntiles)), block(kBlock);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(scan_tile<V, Load>, tiles, block, 0, st, L, n, tsum);
-        if (e != hipSuccess) return e;
-    }
-    e = launch_kernel(scan_carry<V>, dim3(1), block, 0, st, tsum, ntiles, out + n);
-    if (e != hipSuccess || !ntiles) return e;
-    return launch_kernel(scan_place<V, Load>, tiles, block, 0, st, L, n, static_cast<const V*>(tsum), out);
-}
 
 // ---------------------------------------------------------------- one connection
 

@@ -184,6 +184,9 @@ _PROTOS = {
     "sccsum_tcp_tx_data_max_blocks": (ctypes.c_int, []),
     "sccsum_tcp_tx_data": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp]),
+    "sccsum_tcp_rx_acks_workspace": (_u64, [_u64, _u32, _u64]),
+    "sccsum_tcp_rx_acks": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _u64,
+                                          ctypes.c_int64, _vp, _vp, _vp, _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -361,6 +364,36 @@ class TcpTxOpts(ctypes.Structure):
     """sccsum_tcp_tx_opts: what get_transmit_packet takes from hw_features(), and the layout's headroom."""
     _fields_ = [("src_host", ctypes.c_uint32), ("mtu", ctypes.c_uint32), ("max_packet_len", ctypes.c_uint32),
                 ("headroom", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+TCP_ACK_ELIGIBLE = 0x01     # sccsum_tcp_ack.flags: the tcb may take the advancing-ACK path
+TCP_ACK_CLOSE_WAIT = 0x02   # the state is CLOSE_WAIT: no closing output()
+TCP_ACK_FIRST_SAMPLE = 0x04  # ... and sccsum_tcp_ack_run.flags: _snd.first_rto_sample
+TCP_ACK_ALL_ACKED = 0x08    # run records only: the queue is empty, stop the timer, signal_all_data_acked
+TCP_ACK_RTX_REARM = 0x10    # run records only: rearm the retransmit timer at now + rto
+TCP_ACK_POLL = 0x20         # run records only: clear_delayed_ack(); output()
+TCP_STOP_DATA = 9           # sccsum_tcp_ack_run.stop: the segment carries text
+TCP_STOP_WL = 10            # ... or fails the SND.WL1 / WL2 test at the run's head
+TCP_ACK_MAX_ENTRIES = 1 << 31
+
+
+class TcpAck(ctypes.Structure):
+    """sccsum_tcp_ack: the send-side state of one tcb as tcp_rx_acks takes it (64 bytes)."""
+    _fields_ = [("una", ctypes.c_uint32), ("next", ctypes.c_uint32), ("window", ctypes.c_uint32),
+                ("wl1", ctypes.c_uint32), ("wl2", ctypes.c_uint32), ("cwnd", ctypes.c_uint32),
+                ("ssthresh", ctypes.c_uint32), ("unsent_len", ctypes.c_uint32), ("rcv_next", ctypes.c_uint32),
+                ("rto", ctypes.c_uint32), ("srtt", ctypes.c_int64), ("rttvar", ctypes.c_int64),
+                ("mss", ctypes.c_uint16), ("window_scale", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint32)]
+
+
+class TcpAckRun(ctypes.Structure):
+    """sccsum_tcp_ack_run: what one run's taken ACKs did to its tcb (64 bytes)."""
+    _fields_ = [("taken", ctypes.c_uint32), ("una", ctypes.c_uint32), ("acked", ctypes.c_uint32),
+                ("popped", ctypes.c_uint32), ("trim", ctypes.c_uint32), ("queue_freed", ctypes.c_uint32),
+                ("window", ctypes.c_uint32), ("cwnd", ctypes.c_uint32), ("srtt", ctypes.c_int64),
+                ("rttvar", ctypes.c_int64), ("rto", ctypes.c_uint32), ("flags", ctypes.c_uint8),
+                ("stop", ctypes.c_uint8), ("pad", ctypes.c_uint16), ("reserved", ctypes.c_uint32 * 2)]
 
 
 class Fragment(ctypes.Structure):
