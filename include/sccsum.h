@@ -1976,6 +1976,157 @@ int sccsum_tcp_rx_acks(const sccsum_tcp_seg* d_seg, const uint32_t* d_first, con
                        const int64_t* d_q_tx, uint64_t nq, int64_t now_ns, sccsum_tcp_ack_run* d_run, uint64_t* d_total,
                        void* d_workspace, void* stream);
 
+/* ---- TCP passive open: the SYNs of tcp_rx's LISTEN bucket become connections ------------
+ * A segment with no tcb on a listening port takes the rest of tcp::received
+ * (include/seastar/net/tcp.hh:888-929): listener->full(), the RST / ACK / SYN
+ * triage, respond_with_reset, and for a SYN input_handle_listen_state
+ * (tcp.hh:1115-1141): tcp_option::parse (src/net/tcp.cc:34-79), init_from_options
+ * (tcp.hh:1079-1112), get_isn (tcp.hh:2067-2086) and the SYN-ACK of output_one with
+ * tcp_option::fill (tcp.cc:81-138).  sccsum_tcp_listen does this for bucket 1 of a
+ * finished sccsum_tcp_rx, in arrival order, up to the first segment whose outcome
+ * needs a tcb made by this very batch; from there on the host walks, in order,
+ * with its real _tcbs, so no outcome depends on the device.
+ *
+ * Inputs: the frames batch of the tcp_rx call (d_bytes, bytes_len, d_off, nbatch)
+ * and its outputs d_first, d_order, d_seg, d_src as they stand on the device (no
+ * host synchronisation, capturable).  The bucket is positions d_first[1] ..
+ * d_first[2]; position i of the bucket (0-based, arrival order) is the rule's i.
+ * m_max is the caller's upper bound of the bucket's size: it sizes the grids and
+ * the workspace, and a longer bucket is read as cut to m_max.  The local address
+ * of a segment is its frame's IPv4 destination, bytes 16..19 at
+ * d_off[d_order[..]] (read as 0 where that lies outside the buffer); the option
+ * bytes are the hdr_len - 20 bytes before pay_off (read as none where they lie
+ * outside the buffer).  No payload byte is read.  d_space[65536] (device memory):
+ * entry p is max_size - (_pending + _q.size()) of port p's listener at the start
+ * of the batch, 0 when the port is full already.  opts, by value: isn_key, the 64
+ * bytes of isn_secret::key as sixteen native words; isn_m, microseconds since the
+ * epoch / 4, truncated to 32 bits; mtu (68..65535): local_mss = mtu - 40; flags:
+ * SCCSUM_TCP_CSUM_OFFLOAD for the resets, as in sccsum_tcp_rx.
+ *
+ * The rule, p = the segment's dport:
+ *   eligible       SYN set, RST and ACK clear (tcp.hh:902-914); FIN, PSH, URG and a
+ *                  payload do not matter
+ *   candidate      a connid's first eligible segment; its rank is the number of
+ *                  earlier candidates on the same port
+ *   created        a candidate with rank < d_space[p] at a position before `taken`.
+ *                  _pending + _q.size() never decreases inside a batch (its only
+ *                  decrement, add_connected_tcb, pushes to _q in the same step,
+ *                  tcp.hh:767-772), so port p is full behind its d_space[p]-th
+ *                  created candidate and stays full; with d_space[p] == 0 it is
+ *                  full from the start
+ *   taken          the first position whose connid has a created candidate before
+ *                  it (the bucket's size when there is none): there the host's
+ *                  _tcbs decides — an RST can erase a SYN_RECEIVED tcb and the
+ *                  connid be created again, which changes full() behind it
+ * d_class[i] for the positions before `taken`, decided in this order:
+ *   SCCSUM_TCP_LISTEN_RESET   the port is full at i, RST clear (tcp.hh:890-898)
+ *   SCCSUM_TCP_LISTEN_DROP    the port is full at i, RST set (tcp.hh:983-985)
+ *   SCCSUM_TCP_LISTEN_DROP    RST set (tcp.hh:902-905)
+ *   SCCSUM_TCP_LISTEN_RESET   ACK set (tcp.hh:907-912)
+ *   SCCSUM_TCP_LISTEN_NEW     SYN set: a created candidate (tcp.hh:914-924)
+ *   SCCSUM_TCP_LISTEN_DROP    no RST, ACK or SYN (tcp.hh:925-928)
+ * and SCCSUM_TCP_LISTEN_LATER for every position >= taken: nothing else is
+ * written for it and it creates nothing.  The host applies the records (each
+ * created tcb counts in the _pending its walk uses) and then walks the positions
+ * from `taken` on in order.
+ *
+ * Outputs (K created connections, in arrival order):
+ *   d_class[m_max]  u8, as above
+ *   d_new[K]        64 bytes each, 16-byte aligned, room for m_max: the connid;
+ *                   pos = i; irs = SEG.SEQ; iss; snd_mss (536 when none was parsed);
+ *                   local_mss; snd_wscale; rcv_wscale (7 iff a window-scale option
+ *                   was parsed, else 0); snd_window = window << snd_wscale; cwnd = 2,
+ *                   3 or 4 snd_mss (tcp.hh:1102-1108); ssthresh = snd_window;
+ *                   rcv_window = 29200 << rcv_wscale; wl1 = SEG.SEQ, wl2 = SEG.ACK;
+ *                   flags SCCSUM_TCP_NEW_*; reserved written as 0.  snd_wscale > 14
+ *                   sets _WSCALE_BIG and keeps snd_window = ssthresh = window
+ *                   unshifted (the reference's uint16 << shift is undefined from
+ *                   some values on); the SYN-ACK does not depend on it
+ *   d_synack        32 K bytes, 4-byte aligned, room for 32 m_max: slot k holds
+ *                   tcp_option::fill's bytes for SYN|ACK at [32 k + 20, 32 k +
+ *                   hdr_len): MSS (local_mss) iff one was received, window scale 7
+ *                   iff one was received, NOP padding and EOL; hdr_len 20, 24 or 28.
+ *                   The bytes from there to 32 k + 32 are written as 0; the twenty
+ *                   in front are sccsum_tcp_send's and are not touched
+ *   d_sa_off[K], d_sa_len[K], d_sa_out[K]   32 k + hdr_len (u64), 0, and a complete
+ *                   sccsum_tcp_out: dst the foreign address, seq = iss, ack = irs +
+ *                   1, the ports swapped, window 29200, flags 0x12, hdr_len, mss =
+ *                   snd_mss.  With d_synack they are sccsum_tcp_send's batch as they
+ *                   stand; sccsum_spans and sccsum_ipv4_send follow with no host step
+ *   d_rst, d_rst_dst   the RESET segments answered exactly as sccsum_tcp_rx's list
+ *                   is written, stable in arrival order; room for 20 m_max bytes
+ *                   and m_max words
+ *   d_total[4]      {taken, K, resets, dropped}, 8-byte aligned
+ * iss = the first four digest bytes of MD5, little-endian, + isn_m, mod 2^32; the
+ * message is {local_ip, foreign_ip, (local_port << 16) + foreign_port} as three
+ * native words and the 64 key bytes: 76 bytes, two blocks, computed in the lane.
+ *
+ * The options follow tcp_option::parse's loop literally, its fixed advances
+ * included (MSS by 4, window scale by 3, SACK by 2, whatever the length byte
+ * says; an unknown kind by its length byte, ending at length 0).  Two deviations:
+ * where the reference would read a byte at or past opt_end (a kind other than NOP
+ * / EOL in the last position; an MSS or window scale whose value bytes lie past
+ * the end) its behaviour is undefined, and the device ends the parse there and
+ * keeps what it parsed before; and the device never reads outside [pay_off -
+ * (hdr_len - 20), pay_off).
+ *
+ * Each connid's first eligible segment is found with a hash table in the
+ * workspace: 2^bits slots of one word, 2^bits the smallest power of two >=
+ * max(16, 2 m_max), the home slot sccsum_tcp_conns_slot(connid, bits), linear
+ * probing; a slot holds the smallest position of its connid, decided by an atomic
+ * min on that value.  Which slot a connid takes depends on arrival, the value
+ * does not, and no atomic decides where an output lands: the ranks come from a
+ * stable radix sort of the candidates by port (two 8-bit digits) and the lists
+ * from stable compactions, so two runs give identical bytes.  Plain dependent
+ * launches on `stream`, no allocation, no memset.  d_workspace:
+ * sccsum_tcp_listen_workspace(m_max) bytes, 16-byte aligned.  No output may
+ * overlap another array of the call.  SCCSUM_EINVAL before any device work: a
+ * NULL required pointer (d_total and the workspace always; with m_max != 0 every
+ * other one, d_bytes unless bytes_len == 0 and d_off unless nbatch == 0),
+ * misalignment (d_new and the workspace 16; d_off, d_seg, d_sa_off and d_total 8;
+ * the 32-bit arrays, d_synack, d_sa_out and d_rst 4), m_max >
+ * SCCSUM_TCP_LISTEN_MAX, nbatch > 2^32 - 1, mtu outside 68..65535, unknown flags,
+ * a stream of another device than the current one.  m_max == 0 writes d_total
+ * (all 0) and is SCCSUM_OK. */
+#define SCCSUM_TCP_LISTEN_NEW   0u
+#define SCCSUM_TCP_LISTEN_RESET 1u
+#define SCCSUM_TCP_LISTEN_DROP  2u
+#define SCCSUM_TCP_LISTEN_LATER 3u
+#define SCCSUM_TCP_LISTEN_MAX (1u << 30)
+#define SCCSUM_TCP_NEW_MSS        0x01u /* _mss_received */
+#define SCCSUM_TCP_NEW_WSCALE     0x02u /* _win_scale_received */
+#define SCCSUM_TCP_NEW_SACK       0x04u /* _sack_received */
+#define SCCSUM_TCP_NEW_WSCALE_BIG 0x08u /* snd_wscale > 14: snd_window and ssthresh are unshifted */
+
+typedef struct sccsum_tcp_new {
+    uint32_t local_ip, foreign_ip;
+    uint16_t local_port, foreign_port;
+    uint32_t pos;      /* the position in the bucket */
+    uint32_t irs, iss;
+    uint32_t snd_window, cwnd;
+    uint32_t ssthresh, rcv_window;
+    uint32_t wl1, wl2;
+    uint16_t snd_mss, local_mss;
+    uint8_t snd_wscale, rcv_wscale;
+    uint8_t flags;     /* SCCSUM_TCP_NEW_* */
+    uint8_t pad;
+    uint32_t reserved[2]; /* written as 0 */
+} sccsum_tcp_new;
+typedef struct sccsum_tcp_listen_opts {
+    uint32_t isn_key[16]; /* isn_secret::key */
+    uint32_t isn_m;       /* microseconds since the epoch / 4, mod 2^32 */
+    uint32_t mtu;         /* hw_features().mtu, 68..65535 */
+    uint32_t flags;       /* SCCSUM_TCP_CSUM_OFFLOAD */
+} sccsum_tcp_listen_opts;
+
+uint64_t sccsum_tcp_listen_workspace(uint64_t m_max);
+int sccsum_tcp_listen(sccsum_tcp_listen_opts opts, const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off,
+                      uint64_t nbatch, const uint32_t* d_first, const uint32_t* d_order, const sccsum_tcp_seg* d_seg,
+                      const uint32_t* d_src, uint64_t m_max, const uint32_t* d_space, uint8_t* d_class,
+                      sccsum_tcp_new* d_new, void* d_synack, uint64_t* d_sa_off, uint32_t* d_sa_len,
+                      sccsum_tcp_out* d_sa_out, void* d_rst, uint32_t* d_rst_dst, uint64_t* d_total, void* d_workspace,
+                      void* stream);
+
 /* Pinned (page-locked) host memory for packet pools. */
 int sccsum_host_alloc(void** p, uint64_t bytes);
 int sccsum_host_free(void* p);

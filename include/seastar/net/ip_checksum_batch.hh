@@ -1125,6 +1125,57 @@ public:
     }
 };
 
+// TCP rx, the passive open (<sccsum.h> sccsum_tcp_listen): what tcp::received
+// does with the segments of tcp_rx's LISTEN bucket (tcp.hh:888-929) — full(),
+// the RST / ACK / SYN triage, and per new connection input_handle_listen_state
+// with the options parsed, the ISN, one record and the staged SYN-ACK — up to
+// the first segment that needs a tcb of this very batch; from there the host
+// walks in order.  Only the option bytes of the frames are read.
+//   tcp_listen listen({key..., isn_m, 1500, 0});
+//   listen.run(ip, rx_out, m_max, d_space, out, d_ws, stream);   // rx_out: what tcp_rx::run wrote
+//   tx.run(out.synack, 32 * total[1], out.sa_off, out.sa_len, out.sa_out, total[1], tx_out, stream);
+class tcp_listen {
+    sccsum_tcp_listen_opts _opts;
+
+    static void check(int rc, const char* what) {
+        if (rc != SCCSUM_OK) {
+            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+        }
+    }
+
+public:
+    // what run() writes (device arrays with room for m_max entries; <sccsum.h>, "TCP passive open")
+    struct outputs {
+        uint8_t* cls = nullptr;              // m_max
+        sccsum_tcp_new* rec = nullptr;       // m_max, 16-byte aligned
+        void* synack = nullptr;              // 32 m_max bytes
+        uint64_t* sa_off = nullptr;          // m_max
+        uint32_t* sa_len = nullptr;          // m_max
+        sccsum_tcp_out* sa_out = nullptr;    // m_max
+        void* rst = nullptr;                 // 20 m_max bytes
+        uint32_t* rst_dst = nullptr;         // m_max
+        uint64_t* total = nullptr;           // 4: taken, created, resets, dropped
+    };
+
+    explicit tcp_listen(const sccsum_tcp_listen_opts& opts) : _opts(opts) {}
+
+    const sccsum_tcp_listen_opts& opts() const noexcept { return _opts; }
+    // the batch's one clock_type::now(): microseconds since the epoch / 4
+    void set_isn_m(uint32_t isn_m) noexcept { _opts.isn_m = isn_m; }
+
+    static uint64_t workspace(uint64_t m_max) noexcept { return sccsum_tcp_listen_workspace(m_max); }
+
+    // ip: the batch tcp_rx::run was given; rx: its outputs as they stand on the device; m_max: an upper bound of
+    // the LISTEN bucket's size (tcp_rx's n always is one); d_space: 65536 words, the room left per listening port
+    void run(const device_packet_batch& ip, const tcp_rx::outputs& rx, uint64_t m_max, const uint32_t* d_space,
+             const outputs& out, void* d_workspace, void* stream) const {
+        check(sccsum_tcp_listen(_opts, ip.bytes, ip.bytes_len, ip.off, ip.n, rx.first, rx.order, rx.seg, rx.src, m_max,
+                                d_space, out.cls, out.rec, out.synack, out.sa_off, out.sa_len, out.sa_out, out.rst,
+                                out.rst_dst, out.total, d_workspace, stream),
+              "sccsum_tcp_listen");
+    }
+};
+
 }  // namespace net
 
 }  // namespace seastar

@@ -2317,6 +2317,169 @@ def tcp_rx_acks(rx: TcpRxResult, ack_state: torch.Tensor, queue: TcpAckQueues, n
     return TcpRxAcksResult(rx=rx, run=run.view(torch.uint8).view(-1, 64), total=total)
 
 
+TCP_NEW_DTYPE = np.dtype([("local_ip", "<u4"), ("foreign_ip", "<u4"), ("local_port", "<u2"), ("foreign_port", "<u2"),
+                          ("pos", "<u4"), ("irs", "<u4"), ("iss", "<u4"), ("snd_window", "<u4"), ("cwnd", "<u4"),
+                          ("ssthresh", "<u4"), ("rcv_window", "<u4"), ("wl1", "<u4"), ("wl2", "<u4"), ("snd_mss", "<u2"),
+                          ("local_mss", "<u2"), ("snd_wscale", "u1"), ("rcv_wscale", "u1"), ("flags", "u1"),
+                          ("pad", "u1"), ("reserved", "<u4", (2,))])
+TCP_PORTS = 65536
+
+
+@dataclass
+class TcpListenResult:
+    """What sccsum_tcp_listen wrote (include/sccsum.h, "TCP passive open"):
+    the LISTEN bucket of a tcp_rx up to the first segment that needs a tcb
+    this very batch created."""
+    rx: TcpRxResult
+    cls: torch.Tensor          # uint8 [m_max]: native.TCP_LISTEN_* per position of the bucket
+    rec: torch.Tensor          # uint8 [m_max, 64]: sccsum_tcp_new records (TCP_NEW_DTYPE on the host)
+    synack: torch.Tensor       # uint8 [32 m_max]: the SYN-ACK staging, 32 bytes a created connection
+    sa_off: torch.Tensor       # int64 [m_max]: 32 k + hdr_len
+    sa_len: torch.Tensor       # int32 [m_max]: 0
+    sa_out: torch.Tensor       # uint8 [m_max, 24]: sccsum_tcp_out records
+    rst: torch.Tensor          # uint8 [>= 20 m_max]: the RST answers, 20 bytes each
+    rst_dst: torch.Tensor      # int32 [m_max]: their destinations
+    total: torch.Tensor        # int64 [4]: taken, created, resets, dropped
+    _totals: tuple | None = None
+    _new: np.ndarray | None = None
+
+    def totals(self) -> tuple:
+        """(taken, created, resets, dropped) on the host (synchronises once)."""
+        if self._totals is None:
+            self._totals = tuple(int(x) for x in self.total.cpu().numpy().view(np.uint64))
+        return self._totals
+
+    def new(self) -> np.ndarray:
+        """The records of the created connections on the host as TCP_NEW_DTYPE, in arrival order."""
+        if self._new is None:
+            k = self.totals()[1]
+            self._new = self.rec[:k].cpu().numpy().reshape(-1).view(TCP_NEW_DTYPE)
+        return self._new
+
+    def classes(self) -> torch.Tensor:
+        """The class of every position of the bucket (a view; positions from
+        totals()[0] on are TCP_LISTEN_LATER: the host's to walk, in order)."""
+        b = self.rx.bounds()
+        return self.cls[:min(int(b[2] - b[1]), int(self.cls.numel()))]
+
+    @property
+    def synacks(self) -> tuple:
+        """(payloads, out): what tcp_send takes for the SYN-ACKs — empty
+        payloads behind hdr_len bytes of headroom whose options are written,
+        and their sccsum_tcp_out records."""
+        k = self.totals()[1]
+        return (PacketBatch(data=self.synack, off=self.sa_off[:k], length=self.sa_len[:k], bytes_len=32 * k, max_len=0),
+                self.sa_out[:k])
+
+    @property
+    def resets(self) -> tuple:
+        """(l4, dst): the RST answers as TcpRxResult.resets gives tcp_rx's."""
+        k = self.totals()[2]
+        dev = self.rst.device
+        off = torch.arange(k, dtype=torch.int64, device=dev) * 20
+        length = torch.full((k,), 20, dtype=torch.int32, device=dev)
+        return (PacketBatch(data=self.rst, off=off, length=length, bytes_len=20 * k, max_len=20 if k else 0),
+                self.rst_dst[:k])
+
+    def later(self) -> torch.Tensor:
+        """The records of the positions the host still walks, in order: segs of the bucket from `taken` on."""
+        b = self.rx.bounds()
+        return self.rx.seg[int(b[1]) + self.totals()[0]:int(b[2])]
+
+
+def _isn_key(key) -> tuple:
+    if isinstance(key, (bytes, bytearray)):
+        if len(key) != 64:
+            raise ValueError("key: need the 64 bytes of isn_secret::key")
+        return tuple(int(x) for x in np.frombuffer(bytes(key), dtype="<u4"))
+    words = [int(x) for x in key]
+    if len(words) != 16 or any(not 0 <= w <= 0xFFFFFFFF for w in words):
+        raise ValueError("key: need 64 bytes or sixteen 32-bit words")
+    return tuple(words)
+
+
+def tcp_listen_check(rx, b, space, key, isn_m, mtu, flags=0, m_max=None) -> tuple:
+    """What tcp_listen refuses before any launch; returns (m_max, nbatch, key words)."""
+    if not isinstance(rx, TcpRxResult):
+        raise ValueError("rx: need the TcpRxResult of tcp_rx")
+    if not isinstance(b, PacketBatch):
+        raise ValueError("b: need the PacketBatch tcp_rx was given")
+    dev = rx.seg.device
+    if b.device != dev:
+        raise ValueError(f"b: the frames live on {b.device}, rx on {dev}")
+    nbatch = b.n
+    if nbatch > 0xFFFFFFFF:
+        raise ValueError("b: at most 2^32-1 frames")
+    n = int(rx.seg.shape[0])
+    m = n if m_max is None else int(m_max)
+    if not 0 <= m <= min(n, native.TCP_LISTEN_MAX):
+        raise ValueError(f"m_max: need 0..{min(n, native.TCP_LISTEN_MAX)} (the segments of rx, at most 2^30)")
+    if isinstance(space, dict):
+        for port, room in space.items():
+            if not 0 <= int(port) < TCP_PORTS or not 0 <= int(room) <= 0xFFFFFFFF:
+                raise ValueError(f"space: need {{port 0..65535: room 0..2^32-1}}, got {port}: {room}")
+    elif not isinstance(space, torch.Tensor) or space.dim() != 1 or int(space.numel()) != TCP_PORTS:
+        raise ValueError("space: need a {port: room} dict or a 1-D int32 tensor of 65536 entries")
+    else:
+        _need(space, TCP_PORTS, torch.int32, "space", dev)
+    words = _isn_key(key)
+    if not 0 <= int(isn_m) <= 0xFFFFFFFF:
+        raise ValueError("isn_m: need microseconds / 4 truncated to 32 bits")
+    if not 68 <= int(mtu) <= 65535:
+        raise ValueError(f"mtu: need 68..65535, got {mtu}")
+    if int(flags) & ~native.TCP_CSUM_OFFLOAD:
+        raise ValueError(f"flags: unknown bits in {int(flags):#x}")
+    return m, nbatch, words
+
+
+def tcp_listen(rx: TcpRxResult, b: PacketBatch, space, key, isn_m: int, mtu: int, flags: int = 0, stream=None,
+               m_max: int | None = None) -> TcpListenResult:
+    """sccsum_tcp_listen: the passive open for the LISTEN bucket of a tcp_rx —
+    listener->full(), the RST / ACK / SYN triage, and for every new connection
+    the options parsed, the ISN, its record and its SYN-ACK (tcp.hh:888-929,
+    1079-1141, 2067-2086; tcp.cc:34-138).
+
+        ls = tcp_listen(r, ip, {80: 128}, secret, now_us // 4, 1500)   # space: room left per listening port
+        for c in ls.new(): ...                         # make the tcb, inc_pending
+        pay, out = ls.synacks                          # -> tcp_send(pay, out, me, 1500) -> spans -> ipv4_send
+        l4, dst = ls.resets                            # -> ipv4_send(l4, dst, proto 6, ...)
+        ls.later()                                     # the host walks these with its real _tcbs, in order
+
+    m_max (default: every segment of rx) bounds the bucket's size without a
+    host synchronisation; it sizes the outputs and the workspace."""
+    lib = native.load()
+    m, nbatch, words = tcp_listen_check(rx, b, space, key, isn_m, mtu, flags, m_max)
+    dev = rx.seg.device
+    if isinstance(space, dict):
+        host = np.zeros(TCP_PORTS, dtype=np.uint32)
+        for port, room in space.items():
+            host[int(port)] = int(room)
+        space = torch.from_numpy(host.view(np.int32)).to(dev)
+    k = max(m, 1)
+    cls = _scratch(k, dev, stream, torch.uint8)
+    rec = _scratch(8 * k, dev, stream, torch.int64)
+    synack = _scratch(4 * k, dev, stream, torch.int64)
+    sa_off = _scratch(k, dev, stream, torch.int64)
+    sa_len = _scratch(k, dev, stream, torch.int32)
+    sa_out = _scratch(6 * k, dev, stream, torch.int32)
+    rst = _scratch(5 * k + 3, dev, stream, torch.int32)
+    rst_dst = _scratch(k, dev, stream, torch.int32)
+    total = _scratch(4, dev, stream, torch.int64)
+    ws = _scratch(int(lib.sccsum_tcp_listen_workspace(m)), dev, stream)
+    opts = native.TcpListenOpts((ctypes.c_uint32 * 16)(*words), int(isn_m), int(mtu), int(flags))
+    empty = m == 0  # an empty tensor has no address
+    code = lib.sccsum_tcp_listen(
+        opts, ctypes_ptr(b.data), b.bytes_len, None if nbatch == 0 else ctypes_ptr(b.off), nbatch,
+        ctypes_ptr(rx.first), None if empty else ctypes_ptr(rx.order), None if empty else ctypes_ptr(rx.seg),
+        None if empty else ctypes_ptr(rx.src_all), m, ctypes_ptr(space), ctypes_ptr(cls), ctypes_ptr(rec),
+        ctypes_ptr(synack), ctypes_ptr(sa_off), ctypes_ptr(sa_len), ctypes_ptr(sa_out), ctypes_ptr(rst),
+        ctypes_ptr(rst_dst), ctypes_ptr(total), ctypes_ptr(ws), _stream(stream))
+    native.check(code, "sccsum_tcp_listen")
+    return TcpListenResult(rx=rx, cls=cls[:m], rec=rec.view(torch.uint8).view(-1, 64)[:m], synack=synack.view(torch.uint8),
+                           sa_off=sa_off[:m], sa_len=sa_len[:m], sa_out=sa_out.view(torch.uint8).view(-1, 24)[:m],
+                           rst=rst.view(torch.uint8), rst_dst=rst_dst[:m], total=total)
+
+
 class Engine:
     """sccsum_engine_*: ONE resident grid that takes steps (up to 4 batches
     each: a step's tx and rx halves, a shard's rx queues) while it runs, so the

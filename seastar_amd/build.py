@@ -14,7 +14,7 @@ from .native import LIB_PATH, PKG_DIR, REPO_DIR
 
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in
-           ("sccsum.hip", "steer.hip", "send.hip", "reasm.hip", "eth.hip", "udp.hip", "tcp.hip", "tcp_data.hip", "tcp_tx_data.hip", "tcp_ack.hip", "checksummer.cc", "pipeline.cc", "burst.cc")]
+           ("sccsum.hip", "steer.hip", "send.hip", "reasm.hip", "eth.hip", "udp.hip", "tcp.hip", "tcp_data.hip", "tcp_tx_data.hip", "tcp_ack.hip", "tcp_listen.hip", "checksummer.cc", "pipeline.cc", "burst.cc")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # The AMDGPU atomic optimizer rewrites the kernels' lane-0 atomics into
 # wave-wide ones whose result it reads back where they are issued; the flat

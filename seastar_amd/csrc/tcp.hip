@@ -30,7 +30,7 @@
 //            run_carry_kernel one block: the tiles' counts become prefixes; d_total,
 //                             the closing entry of d_run_first
 //            run_place_kernel d_run_conn, d_run_first
-//            reset_kernel     the answers of bucket 2 -> d_rst, d_rst_dst
+//            reset_kernel     the answers of bucket 2 -> d_rst, d_rst_dst (tcp_reset.h)
 //   The key is the connection index for bucket 0 and nconns + 0 / 1 / 2 for
 //   buckets 1 to 3, so ONE sort yields the grouped order and the bucket bases:
 //   one pass up to 253 connections, two up to 65 533, three beyond.
@@ -45,6 +45,7 @@
 #include "bucket_pass.h"
 #include "host_launch.h"
 #include "sccsum.h"
+#include "tcp_reset.h"
 #include "wave_scan.h"
 #include "wire.h"
 
@@ -58,7 +59,6 @@ using host_launch::stream_ok;
 using wave_scan::block_inclusive_scan;
 using wire::be16_at;
 using wire::be32_at;
-using wire::fold16;
 using wire::kMaxDevices;
 using wire::pseudo_seed;
 using wire::tiles_of;
@@ -72,22 +72,18 @@ constexpr uint32_t kTcpHdr = 20;             // tcp_hdr::len
 constexpr uint32_t kProtoTcp = 6;
 constexpr uint32_t kMaxL4 = 65515;           // sccsum_ipv4_send's limit
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kRst = 4u, kSyn = 2u, kAck = 16u;
+constexpr uint32_t kRst = 4u;
 constexpr int kFlatBlock = 256;
 constexpr int kHostOnly = -1;                // device of a table that has no device copy
 constexpr uint32_t kMaxConns = SCCSUM_TCP_MAX_CONNS;
 
 static_assert(sizeof(sccsum_tcp_seg) == 32 && sizeof(sccsum_tcp_out) == 24 && sizeof(sccsum_tcp_conn) == 12, "layout");
 
-__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-
 // ---------------------------------------------------------------- the connection table
 
-// The home slot of a connid: the three key words mixed, then murmur3's finalizer.
+// The home slot of a connid (wire.h: tcp_listen.hip's table takes the same one).
 __host__ __device__ inline uint32_t hash_of(uint32_t local_ip, uint32_t foreign_ip, uint32_t ports) {
-    uint32_t h = local_ip * 0x9E3779B1u;
-    h = (h ^ foreign_ip) * 0x85EBCA6Bu;
-    return wire::fmix32(h ^ ports);
+    return wire::connid_hash(local_ip, foreign_ip, ports);
 }
 
 // Linear probing from the home slot: the connection index, or kNone at the
@@ -367,29 +363,8 @@ __global__ __launch_bounds__(kFlatBlock) void reset_kernel(const uint2* __restri
     const uint64_t r = p - lo;
     const uint2 a = O.seg[4 * p + 1], b = O.seg[4 * p + 2], c = O.seg[4 * p + 3];
     const uint2 ad = addr[kv[p].y];                        // x = src (the foreign address), y = dst (ours)
-    const uint32_t in_seq = a.y, in_ack = b.x;
-    const uint32_t in_sport = c.x >> 16, in_dport = c.y & 0xFFFFu, in_flags = (c.y >> 16) & 0xFFu;
-    const uint32_t seq = (in_flags & kAck) ? in_ack : 0u;
-    const bool syn = (in_flags & kSyn) != 0;
-    const uint32_t ack = syn ? in_seq + 1u : 0u;
-    const uint32_t fl = kRst | (syn ? kAck : 0u);
-    const uint32_t w3 = ((kTcpHdr / 4u) << 28) | (fl << 16);   // data_offset, flags, window 0
-    const uint32_t seed = pseudo_seed(ad.y, ad.x, kProtoTcp, kTcpHdr);
-    uint32_t field;
-    if (flags & SCCSUM_TCP_CSUM_OFFLOAD) {
-        field = seed;                                      // ~csum.get(): the folded sum itself
-    } else {
-        const uint64_t s = uint64_t(seed) + in_dport + in_sport + (seq >> 16) + (seq & 0xFFFFu) + (ack >> 16) +
-                           (ack & 0xFFFFu) + (w3 >> 16);
-        field = 0xFFFFu ^ fold16(s);
-    }
-    uint32_t* const out = O.rst + 5 * r;
-    out[0] = bswap32((in_dport << 16) | in_sport);         // the ports swapped
-    out[1] = bswap32(seq);
-    out[2] = bswap32(ack);
-    out[3] = bswap32(w3);
-    out[4] = bswap32(field << 16);                         // urgent 0
-    O.rst_dst[r] = ad.x;
+    tcp_reset::answer(a.y, b.x, c.x >> 16, c.y & 0xFFFFu, (c.y >> 16) & 0xFFu, ad.x, ad.y, flags, O.rst + 5 * r,
+                      O.rst_dst + r);
 }
 
 // ---------------------------------------------------------------- tx: tcp_send

@@ -40,6 +40,15 @@ __host__ __device__ inline uint32_t fmix32(uint32_t h) {
     return h;
 }
 
+// The home slot of a TCP connid {local_ip, foreign_ip, local_port << 16 |
+// foreign_port}: the three words mixed, then murmur3's finalizer
+// (sccsum_tcp_conns_slot).
+__host__ __device__ inline uint32_t connid_hash(uint32_t local_ip, uint32_t foreign_ip, uint32_t ports) {
+    uint32_t h = local_ip * 0x9E3779B1u;
+    h = (h ^ foreign_ip) * 0x85EBCA6Bu;
+    return fmix32(h ^ ports);
+}
+
 // The caller's status masks: every bit of `need`, none of `reject`.
 __device__ __forceinline__ bool status_passes(uint32_t st, uint32_t need, uint32_t reject) {
     return (st & need) == need && (st & reject) == 0;

@@ -187,6 +187,10 @@ _PROTOS = {
     "sccsum_tcp_rx_acks_workspace": (_u64, [_u64, _u32, _u64]),
     "sccsum_tcp_rx_acks": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _u64,
                                           ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "sccsum_tcp_listen_workspace": (_u64, [_u64]),
+    # the first argument, sccsum_tcp_listen_opts by value, is put in front where TcpListenOpts is defined
+    "sccsum_tcp_listen": (ctypes.c_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 PIPE_SPANS = 0
 PIPE_IPV4 = 1
@@ -394,6 +398,38 @@ class TcpAckRun(ctypes.Structure):
                 ("window", ctypes.c_uint32), ("cwnd", ctypes.c_uint32), ("srtt", ctypes.c_int64),
                 ("rttvar", ctypes.c_int64), ("rto", ctypes.c_uint32), ("flags", ctypes.c_uint8),
                 ("stop", ctypes.c_uint8), ("pad", ctypes.c_uint16), ("reserved", ctypes.c_uint32 * 2)]
+
+
+TCP_LISTEN_NEW = 0          # tcp_listen classes: a created connection (a record and a SYN-ACK)
+TCP_LISTEN_RESET = 1        # answered with a RST: the port is full, or an ACK in LISTEN
+TCP_LISTEN_DROP = 2         # discarded: a RST, or no RST / ACK / SYN
+TCP_LISTEN_LATER = 3        # at or behind `taken`: the host walks it with its real _tcbs
+TCP_LISTEN_MAX = 1 << 30
+TCP_NEW_MSS = 0x01          # sccsum_tcp_new.flags: _mss_received
+TCP_NEW_WSCALE = 0x02       # _win_scale_received
+TCP_NEW_SACK = 0x04         # _sack_received
+TCP_NEW_WSCALE_BIG = 0x08   # snd_wscale > 14: snd_window and ssthresh are unshifted
+TCP_RCV_WINDOW = 29200      # get_default_receive_window_size before the shift
+
+
+class TcpNew(ctypes.Structure):
+    """sccsum_tcp_new: one connection tcp_listen created (64 bytes)."""
+    _fields_ = [("local_ip", ctypes.c_uint32), ("foreign_ip", ctypes.c_uint32), ("local_port", ctypes.c_uint16),
+                ("foreign_port", ctypes.c_uint16), ("pos", ctypes.c_uint32), ("irs", ctypes.c_uint32),
+                ("iss", ctypes.c_uint32), ("snd_window", ctypes.c_uint32), ("cwnd", ctypes.c_uint32),
+                ("ssthresh", ctypes.c_uint32), ("rcv_window", ctypes.c_uint32), ("wl1", ctypes.c_uint32),
+                ("wl2", ctypes.c_uint32), ("snd_mss", ctypes.c_uint16), ("local_mss", ctypes.c_uint16),
+                ("snd_wscale", ctypes.c_uint8), ("rcv_wscale", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("pad", ctypes.c_uint8), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class TcpListenOpts(ctypes.Structure):
+    """sccsum_tcp_listen_opts: the ISN secret and clock, the MTU, the flags; passed by value (76 bytes)."""
+    _fields_ = [("isn_key", ctypes.c_uint32 * 16), ("isn_m", ctypes.c_uint32), ("mtu", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
+_PROTOS["sccsum_tcp_listen"] = (ctypes.c_int, [TcpListenOpts] + _PROTOS["sccsum_tcp_listen"][1])
 
 
 class Fragment(ctypes.Structure):
