@@ -59,6 +59,39 @@ namespace seastar {
 
 namespace net {
 
+namespace detail {
+
+// Every error of the C-ABI becomes "<the call>: <sccsum_strerror>".
+inline void check(int rc, const char* what) {
+    if (rc != SCCSUM_OK) {
+        throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
+    }
+}
+
+// The one owner of a C-ABI object: filled through out() by the object's create
+// call, destroyed with it; neither copied nor moved.
+template <typename T, int (*Destroy)(T*)>
+class handle {
+    T* _p = nullptr;
+
+public:
+    handle() = default;
+    handle(const handle&) = delete;
+    handle& operator=(const handle&) = delete;
+    ~handle() { Destroy(_p); }
+
+    T** out() noexcept { return &_p; }
+    T* get() const noexcept { return _p; }
+    // destroy now and report what the destructor cannot
+    void close(const char* what) {
+        T* p = _p;
+        _p = nullptr;
+        check(Destroy(p), what);
+    }
+};
+
+}  // namespace detail
+
 // Packets resident in device memory: one byte buffer plus offset/length
 // arrays (see <sccsum.h> "Memory contract").
 struct device_packet_batch {
@@ -81,15 +114,9 @@ enum class checksum_status : uint8_t {
 class batch_checksummer {
     int _device;
 
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
-
 public:
     // Binds the calling thread (the shard's reactor thread) to `device`.
-    explicit batch_checksummer(int device) : _device(device) { check(sccsum_init(device), "sccsum_init"); }
+    explicit batch_checksummer(int device) : _device(device) { detail::check(sccsum_init(device), "sccsum_init"); }
 
     int device() const noexcept { return _device; }
 
@@ -103,16 +130,17 @@ public:
     // out[i] = checksum of span i, seeded with seeds[i] when seeds != nullptr.
     void sum_spans(const device_packet_batch& b, const uint32_t* d_seeds, uint16_t* d_out, uint8_t* d_status,
                    void* stream) const {
-        check(sccsum_spans(b.bytes, b.bytes_len, b.off, b.len, d_seeds, d_out, d_status, b.n, b.max_len, stream),
-              "sccsum_spans");
+        detail::check(sccsum_spans(b.bytes, b.bytes_len, b.off, b.len, d_seeds, d_out, d_status, b.n, b.max_len,
+                                   stream),
+                      "sccsum_spans");
     }
 
     // out2[2i] = IPv4 header checksum, out2[2i+1] = TCP/UDP checksum of frame i.
     // d_out2 may be null when d_status is given: verify only, 1 status byte
     // written per frame (what the reference keeps of the sum, ip.cc:121-127).
     void ipv4_frames(const device_packet_batch& b, uint16_t* d_out2, uint8_t* d_status, void* stream) const {
-        check(sccsum_ipv4_frames(b.bytes, b.bytes_len, b.off, b.len, d_out2, d_status, b.n, b.max_len, stream),
-              "sccsum_ipv4_frames");
+        detail::check(sccsum_ipv4_frames(b.bytes, b.bytes_len, b.off, b.len, d_out2, d_status, b.n, b.max_len, stream),
+                      "sccsum_ipv4_frames");
     }
 
     // Generate IPv4 header and/or TCP/UDP checksums (ICMP echo replies with
@@ -122,9 +150,9 @@ public:
     // in stream-ordered scratch).  IP fragments get their IPv4 header checksum only.
     void ipv4_fill(const device_packet_batch& b, uint32_t mode, uint16_t* d_out2, uint8_t* d_status,
                    void* stream) const {
-        check(sccsum_ipv4_fill(const_cast<void*>(b.bytes), b.bytes_len, b.off, b.len, d_out2, d_status, b.n,
-                               b.max_len, mode, stream),
-              "sccsum_ipv4_fill");
+        detail::check(sccsum_ipv4_fill(const_cast<void*>(b.bytes), b.bytes_len, b.off, b.len, d_out2, d_status, b.n,
+                                       b.max_len, mode, stream),
+                      "sccsum_ipv4_fill");
     }
 
     // RSS: d_hash[i] = toeplitz_hash(key, forward_hash of frame i) (toeplitz.hh:78-98, net.cc:330-341);
@@ -132,17 +160,17 @@ public:
     // (the reference's rss_key_type: 40 or 52 bytes, at least 4).
     void ipv4_rss(const device_packet_batch& b, const uint8_t* key, size_t key_len, int mode, uint32_t* d_hash,
                   uint8_t* d_status, void* stream) const {
-        check(sccsum_ipv4_rss(b.bytes, b.bytes_len, b.off, b.len, key, static_cast<uint32_t>(key_len), mode, d_hash,
-                              d_status, b.n, stream),
-              "sccsum_ipv4_rss");
+        detail::check(sccsum_ipv4_rss(b.bytes, b.bytes_len, b.off, b.len, key, static_cast<uint32_t>(key_len), mode,
+                                      d_hash, d_status, b.n, stream),
+                      "sccsum_ipv4_rss");
     }
 
     // ipv4_frames and ipv4_rss in one pass over the bytes.
     void ipv4_frames_rss(const device_packet_batch& b, const uint8_t* key, size_t key_len, int mode,
                          uint16_t* d_out2, uint8_t* d_status, uint32_t* d_hash, void* stream) const {
-        check(sccsum_ipv4_frames_rss(b.bytes, b.bytes_len, b.off, b.len, d_out2, d_status, b.n, b.max_len, key,
-                                     static_cast<uint32_t>(key_len), mode, d_hash, stream),
-              "sccsum_ipv4_frames_rss");
+        detail::check(sccsum_ipv4_frames_rss(b.bytes, b.bytes_len, b.off, b.len, d_out2, d_status, b.n, b.max_len, key,
+                                             static_cast<uint32_t>(key_len), mode, d_hash, stream),
+                      "sccsum_ipv4_frames_rss");
     }
 
 #if __cplusplus >= 202002L
@@ -161,15 +189,17 @@ public:
     void spans_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                     const uint32_t* d_len, uint64_t n, uint32_t max_len, const void* d_stage, const uint32_t* d_seeds,
                     uint16_t* d_out, uint8_t* d_status, void* stream) const {
-        check(sccsum_spans_desc(d_desc, d_first, d_off, d_len, d_seeds, d_stage, d_out, d_status, n, max_len, stream),
-              "sccsum_spans_desc");
+        detail::check(sccsum_spans_desc(d_desc, d_first, d_off, d_len, d_seeds, d_stage, d_out, d_status, n, max_len,
+                                        stream),
+                      "sccsum_spans_desc");
     }
 
     void ipv4_frames_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                           const uint32_t* d_len, uint64_t n, uint32_t max_len, const void* d_stage, uint16_t* d_out2,
                           uint8_t* d_status, void* stream) const {
-        check(sccsum_ipv4_frames_desc(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len, stream),
-              "sccsum_ipv4_frames_desc");
+        detail::check(sccsum_ipv4_frames_desc(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len,
+                                              stream),
+                      "sccsum_ipv4_frames_desc");
     }
 
     // ipv4_fill on fragment lists: generate and store the checksums where the
@@ -180,12 +210,12 @@ public:
     void ipv4_fill_desc(const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off,
                         const uint32_t* d_len, uint64_t n, uint32_t max_len, uint32_t mode, void* d_stage,
                         uint16_t* d_out2, uint8_t* d_status, void* stream) const {
-        check(sccsum_ipv4_fill_desc(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len, mode,
-                                    stream),
-              "sccsum_ipv4_fill_desc");
+        detail::check(sccsum_ipv4_fill_desc(d_desc, d_first, d_off, d_len, d_stage, d_out2, d_status, n, max_len, mode,
+                                            stream),
+                      "sccsum_ipv4_fill_desc");
     }
 
-    void sync(void* stream) const { check(sccsum_sync(stream), "sccsum_sync"); }
+    void sync(void* stream) const { detail::check(sccsum_sync(stream), "sccsum_sync"); }
 };
 
 // Burst queue (<sccsum.h> sccsum_burst_*): packets from HOST memory, handed
@@ -206,18 +236,14 @@ class burst_queue {
     static void complete(void* self, uint64_t first, uint32_t count, const uint16_t* results, const uint8_t* status) {
         static_cast<burst_queue*>(self)->_done(first, count, results, status);
     }
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     burst_queue(int device, int mode, uint64_t batch_bytes, uint32_t batch_packets, uint64_t max_delay_ns, int depth,
                 Done done)
         : _done(std::move(done)) {
-        check(sccsum_burst_create(device, mode, batch_bytes, batch_packets, max_delay_ns, depth, &complete, this, &_q),
-              "sccsum_burst_create");
+        detail::check(sccsum_burst_create(device, mode, batch_bytes, batch_packets, max_delay_ns, depth, &complete,
+                                          this, &_q),
+                      "sccsum_burst_create");
     }
     burst_queue(const burst_queue&) = delete;
     burst_queue& operator=(const burst_queue&) = delete;
@@ -227,7 +253,7 @@ public:
     bool submit(const sccsum_fragment* frags, uint32_t nfrag, uint32_t seed = 0, uint64_t* ticket = nullptr) {
         const int rc = sccsum_burst_submit(_q, frags, nfrag, seed, ticket);
         if (rc == SCCSUM_EBUSY) return false;
-        check(rc, "sccsum_burst_submit");
+        detail::check(rc, "sccsum_burst_submit");
         return true;
     }
     // zero-copy: fragments in device-readable pinned / registered host memory,
@@ -235,7 +261,7 @@ public:
     bool submit_mapped(const sccsum_fragment* frags, uint32_t nfrag, uint32_t seed = 0, uint64_t* ticket = nullptr) {
         const int rc = sccsum_burst_submit_mapped(_q, frags, nfrag, seed, ticket);
         if (rc == SCCSUM_EBUSY) return false;
-        check(rc, "sccsum_burst_submit_mapped");
+        detail::check(rc, "sccsum_burst_submit_mapped");
         return true;
     }
     // tx form (SCCSUM_PIPE_IPV4 queues): while a fill mode (SCCSUM_FILL_*) is
@@ -247,15 +273,15 @@ public:
     bool set_fill(uint32_t mode) {
         const int rc = sccsum_burst_set_fill(_q, mode);
         if (rc == SCCSUM_EBUSY) return false;
-        check(rc, "sccsum_burst_set_fill");
+        detail::check(rc, "sccsum_burst_set_fill");
         return true;
     }
     bool poll() {
         int did = 0;
-        check(sccsum_burst_poll(_q, &did), "sccsum_burst_poll");
+        detail::check(sccsum_burst_poll(_q, &did), "sccsum_burst_poll");
         return did != 0;
     }
-    void drain() { check(sccsum_burst_drain(_q), "sccsum_burst_drain"); }
+    void drain() { detail::check(sccsum_burst_drain(_q), "sccsum_burst_drain"); }
 };
 
 // Resident engine (<sccsum.h> sccsum_engine_*): one grid kept on the GPU
@@ -274,48 +300,37 @@ public:
 //   uint64_t b = eng.submit(&rx, 1);
 //   eng.wait(b); eng.wait(a); eng.stop();
 class resident_engine {
-    sccsum_engine* _e = nullptr;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
+    detail::handle<sccsum_engine, sccsum_engine_destroy> _e;
 
 public:
     resident_engine(int device, int mode, uint32_t ring_slots, uint32_t max_in_flight, bool fill = false) {
-        check(sccsum_engine_create(device, mode | (fill ? SCCSUM_ENGINE_FILL : 0), ring_slots, max_in_flight, &_e),
-              "sccsum_engine_create");
+        detail::check(sccsum_engine_create(device, mode | (fill ? SCCSUM_ENGINE_FILL : 0), ring_slots, max_in_flight,
+                                           _e.out()),
+                      "sccsum_engine_create");
     }
     // every limit (ring, in flight, idle and dependency limits; 0 fields = defaults)
     resident_engine(int device, int mode, const sccsum_engine_opts& opts, bool fill = false) {
-        check(sccsum_engine_create_opts(device, mode | (fill ? SCCSUM_ENGINE_FILL : 0), &opts, &_e),
-              "sccsum_engine_create_opts");
+        detail::check(sccsum_engine_create_opts(device, mode | (fill ? SCCSUM_ENGINE_FILL : 0), &opts, _e.out()),
+                      "sccsum_engine_create_opts");
     }
-    resident_engine(const resident_engine&) = delete;
-    resident_engine& operator=(const resident_engine&) = delete;
-    ~resident_engine() { sccsum_engine_destroy(_e); }
     // destroy now, reporting a run that left a published step undone (the destructor cannot)
-    void close() {
-        sccsum_engine* e = _e;
-        _e = nullptr;
-        check(sccsum_engine_destroy(e), "sccsum_engine_destroy");
-    }
+    void close() { _e.close("sccsum_engine_destroy"); }
 
     // launch the grid on `stream` (the calling thread's current device, the engine's)
-    void start(void* stream) { check(sccsum_engine_start(_e, stream), "sccsum_engine_start"); }
+    void start(void* stream) { detail::check(sccsum_engine_start(_e.get(), stream), "sccsum_engine_start"); }
     // false: another engine of this process runs on the device (SCCSUM_EBUSY)
     bool try_start(void* stream) {
-        const int rc = sccsum_engine_start(_e, stream);
+        const int rc = sccsum_engine_start(_e.get(), stream);
         if (rc == SCCSUM_EBUSY) return false;
-        check(rc, "sccsum_engine_start");
+        detail::check(rc, "sccsum_engine_start");
         return true;
     }
     // max_len: the longest packet, if known (sizes the step's tiles; 0 = from bytes_len / n)
     uint64_t submit(const sccsum_batch* batches, uint32_t nbatch, uint64_t timeout_ns = 1'000'000'000,
                     uint32_t max_len = 0) {
         uint64_t step = 0;
-        check(sccsum_engine_submit(_e, batches, nbatch, max_len, timeout_ns, &step), "sccsum_engine_submit");
+        detail::check(sccsum_engine_submit(_e.get(), batches, nbatch, max_len, timeout_ns, &step),
+                      "sccsum_engine_submit");
         return step;
     }
     // in-place fill of every batch (d_out: the values, required); the step returned is done once
@@ -323,14 +338,14 @@ public:
     uint64_t submit_fill(const sccsum_batch* batches, uint32_t nbatch, uint32_t mode,
                          uint64_t timeout_ns = 1'000'000'000, uint32_t max_len = 0) {
         uint64_t step = 0;
-        check(sccsum_engine_submit_fill(_e, batches, nbatch, max_len, mode, timeout_ns, &step),
-              "sccsum_engine_submit_fill");
+        detail::check(sccsum_engine_submit_fill(_e.get(), batches, nbatch, max_len, mode, timeout_ns, &step),
+                      "sccsum_engine_submit_fill");
         return step;
     }
     void wait(uint64_t step, uint64_t timeout_ns = 1'000'000'000) {
-        check(sccsum_engine_wait(_e, step, timeout_ns), "sccsum_engine_wait");
+        detail::check(sccsum_engine_wait(_e.get(), step, timeout_ns), "sccsum_engine_wait");
     }
-    void stop() { check(sccsum_engine_stop(_e), "sccsum_engine_stop"); }
+    void stop() { detail::check(sccsum_engine_stop(_e.get()), "sccsum_engine_stop"); }
 };
 
 // Rx steering (<sccsum.h> sccsum_steer_*): device::hash2cpu / forward_dst
@@ -347,30 +362,17 @@ public:
 //   steer.run(SCCSUM_STEER_HASH2CPU, 0, d_hash, d_status, SCCSUM_ST_OK, SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE,
 //             batch.n, d_cpu, d_order, d_first, d_ws, stream);   // shard c: d_order[d_first[c] .. d_first[c+1])
 class rx_steering {
-    sccsum_steer* _s = nullptr;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
+    detail::handle<sccsum_steer, sccsum_steer_destroy> _s;
 
 public:
     // validates every table entry and copies the tables (host memory) to `device`
     rx_steering(int device, const sccsum_steer_map& map) {
-        check(sccsum_steer_create(device, &map, &_s), "sccsum_steer_create");
+        detail::check(sccsum_steer_create(device, &map, _s.out()), "sccsum_steer_create");
     }
-    rx_steering(const rx_steering&) = delete;
-    rx_steering& operator=(const rx_steering&) = delete;
-    ~rx_steering() { sccsum_steer_destroy(_s); }
-    void close() {
-        sccsum_steer* s = _s;
-        _s = nullptr;
-        check(sccsum_steer_destroy(s), "sccsum_steer_destroy");
-    }
+    void close() { _s.close("sccsum_steer_destroy"); }
 
     // bytes of 16-byte aligned device scratch a run over n packets needs
-    uint64_t workspace(uint64_t n) const noexcept { return sccsum_steer_workspace(_s, n); }
+    uint64_t workspace(uint64_t n) const noexcept { return sccsum_steer_workspace(_s.get(), n); }
 
     // mode SCCSUM_STEER_DISPATCH (forward_dst(src_cpu, hash)) or SCCSUM_STEER_HASH2CPU; a packet whose
     // status lacks a `need` bit or has a `reject` bit is dropped (d_status null: none, masks 0).
@@ -378,20 +380,20 @@ public:
     void run(int mode, uint32_t src_cpu, const uint32_t* d_hash, const uint8_t* d_status, uint32_t need,
              uint32_t reject, uint64_t n, uint8_t* d_cpu, uint32_t* d_order, uint32_t* d_first, void* d_workspace,
              void* stream) const {
-        check(sccsum_steer_run(_s, mode, src_cpu, d_hash, d_status, need, reject, n, d_cpu, d_order, d_first,
-                               d_workspace, stream),
-              "sccsum_steer_run");
+        detail::check(sccsum_steer_run(_s.get(), mode, src_cpu, d_hash, d_status, need, reject, n, d_cpu, d_order,
+                                       d_first, d_workspace, stream),
+                      "sccsum_steer_run");
     }
 
     // qp::build_sw_reta (net.cc:214-231): cpus strictly ascending, as the reference's std::map iterates
     static void build_reta(const uint32_t* cpus, const float* weights, uint32_t n, uint8_t (&reta)[128]) {
-        check(sccsum_steer_build_reta(cpus, weights, n, reta), "sccsum_steer_build_reta");
+        detail::check(sccsum_steer_build_reta(cpus, weights, n, reta), "sccsum_steer_build_reta");
     }
 
     // one hash through the map on the host: device::hash2cpu (SCCSUM_STEER_HASH2CPU) / forward_dst
     static uint32_t dest(const sccsum_steer_map& map, int mode, uint32_t src_cpu, uint32_t hash) {
         const uint32_t d = sccsum_steer_dest(&map, mode, src_cpu, hash);
-        if (d == UINT32_MAX) check(SCCSUM_EINVAL, "sccsum_steer_dest");
+        if (d == UINT32_MAX) detail::check(SCCSUM_EINVAL, "sccsum_steer_dest");
         return d;
     }
 };
@@ -415,12 +417,6 @@ public:
 class rx_reassembler {
     uint32_t _host;
 
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
-
 public:
     // host_address: ipv4::_host_address (host order); 0 accepts every destination
     explicit rx_reassembler(uint32_t host_address) : _host(host_address) {}
@@ -441,18 +437,18 @@ public:
                  uint32_t* d_count, void* d_workspace, void* stream,
                  uint32_t need = SCCSUM_ST_OK | SCCSUM_ST_IPFRAG,
                  uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE) const {
-        check(sccsum_ipv4_frag_records(b.bytes, b.bytes_len, b.off, b.len, d_status, need, reject, b.n, _host, tag,
-                                       d_rec, d_count, d_workspace, stream),
-              "sccsum_ipv4_frag_records");
+        detail::check(sccsum_ipv4_frag_records(b.bytes, b.bytes_len, b.off, b.len, d_status, need, reject, b.n, _host,
+                                               tag, d_rec, d_count, d_workspace, stream),
+                      "sccsum_ipv4_frag_records");
     }
 
     // m records in arrival order, the pending ones of the last run first.  key may be null (then
     // out.d_dgram_hash must be).  Capacity is a prefix rule: what does not fit stays pending.
     void run(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out_bytes, const uint8_t* key, size_t key_len,
              const sccsum_reasm_out& out, void* d_workspace, void* stream) const {
-        check(sccsum_ipv4_reasm(d_rec, m, max_out_bytes, key, static_cast<uint32_t>(key_len), &out, d_workspace,
-                                stream),
-              "sccsum_ipv4_reasm");
+        detail::check(sccsum_ipv4_reasm(d_rec, m, max_out_bytes, key, static_cast<uint32_t>(key_len), &out, d_workspace,
+                                        stream),
+                      "sccsum_ipv4_reasm");
     }
 };
 
@@ -470,12 +466,6 @@ public:
 //   engine.ipv4_fill_desc(out.desc, out.first, out.out_off, out.out_len, frames, mtu, SCCSUM_FILL_IP, ...);
 class tx_sender {
     sccsum_send_opts _opts;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what a run writes (device arrays; sizes in <sccsum.h>, "Tx send")
@@ -503,7 +493,7 @@ public:
     // host arithmetic for one datagram; throws on an MTU outside 68..65535 or unknown flags
     static plan_result plan(const sccsum_send_opts& opts, uint32_t l4_len, uint8_t proto) {
         plan_result r{0, 0};
-        check(sccsum_ipv4_send_plan(&opts, l4_len, proto, &r.frames, &r.out_bytes), "sccsum_ipv4_send_plan");
+        detail::check(sccsum_ipv4_send_plan(&opts, l4_len, proto, &r.frames, &r.out_bytes), "sccsum_ipv4_send_plan");
         return r;
     }
     plan_result plan(uint32_t l4_len, uint8_t proto) const { return plan(_opts, l4_len, proto); }
@@ -519,10 +509,11 @@ public:
              void* d_workspace, void* stream) const {
         sccsum_send_opts o = _opts;
         if (d_l4sum) o.flags |= SCCSUM_SEND_L4;
-        check(sccsum_ipv4_send(&o, const_cast<void*>(l4.bytes), l4.bytes_len, l4.off, l4.len, d_dst, d_proto, d_id,
-                               d_l4sum, l4.n, max_frames, max_out_bytes, out.hdr, out.desc, out.first, out.out_off,
-                               out.out_len, out.dgram_first, out.status, out.total, d_workspace, stream),
-              "sccsum_ipv4_send");
+        detail::check(sccsum_ipv4_send(&o, const_cast<void*>(l4.bytes), l4.bytes_len, l4.off, l4.len, d_dst, d_proto,
+                                       d_id, d_l4sum, l4.n, max_frames, max_out_bytes, out.hdr, out.desc, out.first,
+                                       out.out_off, out.out_len, out.dgram_first, out.status, out.total, d_workspace,
+                                       stream),
+                      "sccsum_ipv4_send");
     }
 };
 
@@ -534,32 +525,23 @@ public:
 //   sccsum_arp_entry e[] = {{0xFFFFFFFFu, 0, 0xFFFFFFFFFFFFull}, {peer_ip, 0, peer_mac}};
 //   arp_table arp(gpu, e, 2);
 class arp_table {
-    sccsum_arp_table* _t = nullptr;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
+    detail::handle<sccsum_arp_table, sccsum_arp_table_destroy> _t;
 
 public:
     // entries: host memory, a later entry for the same ip wins; n <= 2^20
     arp_table(int device, const sccsum_arp_entry* entries, uint32_t n) {
-        check(sccsum_arp_table_create(device, entries, n, &_t), "sccsum_arp_table_create");
+        detail::check(sccsum_arp_table_create(device, entries, n, _t.out()), "sccsum_arp_table_create");
     }
     // no device copy: lookup() alone
     arp_table(const sccsum_arp_entry* entries, uint32_t n) {
-        check(sccsum_arp_table_create_host(entries, n, &_t), "sccsum_arp_table_create_host");
+        detail::check(sccsum_arp_table_create_host(entries, n, _t.out()), "sccsum_arp_table_create_host");
     }
-    arp_table(const arp_table&) = delete;
-    arp_table& operator=(const arp_table&) = delete;
-    ~arp_table() { sccsum_arp_table_destroy(_t); }
 
-    const sccsum_arp_table* get() const noexcept { return _t; }
-    uint32_t bits() const noexcept { return sccsum_arp_table_bits(_t); }
+    const sccsum_arp_table* get() const noexcept { return _t.get(); }
+    uint32_t bits() const noexcept { return sccsum_arp_table_bits(get()); }
 
     // host arithmetic: true and *mac on a hit
-    bool lookup(uint32_t ip, uint64_t* mac) const noexcept { return sccsum_arp_table_lookup(_t, ip, mac) != 0; }
+    bool lookup(uint32_t ip, uint64_t* mac) const noexcept { return sccsum_arp_table_lookup(get(), ip, mac) != 0; }
 
     // a key's home slot in a table of 2^bits slots
     static uint32_t slot(uint32_t ip, uint32_t bits) noexcept { return sccsum_arp_table_slot(ip, bits); }
@@ -580,12 +562,6 @@ class eth_rx {
     uint16_t _protos[SCCSUM_ETH_MAX_PROTOS] = {};
     uint32_t _k = 0;
 
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
-
 public:
     // what run() writes (device arrays; sizes in <sccsum.h>, "Link layer")
     struct outputs {
@@ -599,7 +575,7 @@ public:
 
     // the registered eth_proto values (host order), 1..8 distinct ones: bucket k is protos[k]
     eth_rx(std::initializer_list<uint16_t> protos) {
-        if (protos.size() < 1 || protos.size() > SCCSUM_ETH_MAX_PROTOS) check(SCCSUM_EINVAL, "eth_rx");
+        if (protos.size() < 1 || protos.size() > SCCSUM_ETH_MAX_PROTOS) detail::check(SCCSUM_EINVAL, "eth_rx");
         for (uint16_t p : protos) _protos[_k++] = p;
     }
 
@@ -609,9 +585,9 @@ public:
     static uint64_t learn_workspace(uint64_t n) noexcept { return sccsum_arp_learn_workspace(n); }
 
     void run(const device_packet_batch& wire, const outputs& out, void* d_workspace, void* stream) const {
-        check(sccsum_eth_rx(wire.bytes, wire.bytes_len, wire.off, wire.len, wire.n, _protos, _k, out.cls, out.first,
-                            out.order, out.l3_off, out.l3_len, out.src_mac, d_workspace, stream),
-              "sccsum_eth_rx");
+        detail::check(sccsum_eth_rx(wire.bytes, wire.bytes_len, wire.off, wire.len, wire.n, _protos, _k, out.cls,
+                                    out.first, out.order, out.l3_off, out.l3_len, out.src_mac, d_workspace, stream),
+                      "sccsum_eth_rx");
     }
 
     // ip: an IPv4 bucket; d_status what the frames call wrote for it; d_src_mac the bucket's slice.
@@ -620,10 +596,10 @@ public:
                       uint32_t netmask, const arp_table* table, sccsum_arp_rec* d_rec, uint32_t* d_count,
                       void* d_workspace, void* stream, uint32_t need = SCCSUM_ST_OK,
                       uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE) {
-        check(sccsum_arp_learn_records(ip.bytes, ip.bytes_len, ip.off, ip.len, d_status, need, reject, d_src_mac, ip.n,
-                                       host, netmask, table ? table->get() : nullptr, d_rec, d_count, d_workspace,
-                                       stream),
-              "sccsum_arp_learn_records");
+        detail::check(sccsum_arp_learn_records(ip.bytes, ip.bytes_len, ip.off, ip.len, d_status, need, reject,
+                                               d_src_mac, ip.n, host, netmask, table ? table->get() : nullptr, d_rec,
+                                               d_count, d_workspace, stream),
+                      "sccsum_arp_learn_records");
     }
 };
 
@@ -638,12 +614,6 @@ public:
 //          frames, max_bytes, out, d_ws, stream);
 class eth_tx {
     sccsum_eth_opts _opts;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() writes (device arrays; sizes in <sccsum.h>, "Link layer")
@@ -669,10 +639,10 @@ public:
     void run(const arp_table& table, const uint32_t* d_dst, const uint32_t* d_dgram_first, uint64_t n,
              const sccsum_gather_desc* d_desc, const uint32_t* d_first, const uint64_t* d_off, const uint32_t* d_len,
              uint64_t frames, uint64_t max_out_bytes, const outputs& out, void* d_workspace, void* stream) const {
-        check(sccsum_eth_send(&_opts, table.get(), d_dst, d_dgram_first, n, d_desc, d_first, d_off, d_len, frames,
-                              max_out_bytes, out.eth, out.desc, out.first, out.out_off, out.out_len, out.frame_src,
-                              out.status, out.unresolved, out.total, d_workspace, stream),
-              "sccsum_eth_send");
+        detail::check(sccsum_eth_send(&_opts, table.get(), d_dst, d_dgram_first, n, d_desc, d_first, d_off, d_len,
+                                      frames, max_out_bytes, out.eth, out.desc, out.first, out.out_off, out.out_len,
+                                      out.frame_src, out.status, out.unresolved, out.total, d_workspace, stream),
+                      "sccsum_eth_send");
     }
 };
 
@@ -683,32 +653,23 @@ public:
 //   const uint16_t bound[] = {53, 10000};
 //   udp_ports ports(gpu, bound, 2);
 class udp_ports {
-    sccsum_udp_ports* _t = nullptr;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
+    detail::handle<sccsum_udp_ports, sccsum_udp_ports_destroy> _t;
 
 public:
     // ports: host memory, distinct, host order; channels <= SCCSUM_UDP_MAX_CHANNELS
     udp_ports(int device, const uint16_t* ports, uint32_t channels) {
-        check(sccsum_udp_ports_create(device, ports, channels, &_t), "sccsum_udp_ports_create");
+        detail::check(sccsum_udp_ports_create(device, ports, channels, _t.out()), "sccsum_udp_ports_create");
     }
     // no device copy: lookup() alone
     udp_ports(const uint16_t* ports, uint32_t channels) {
-        check(sccsum_udp_ports_create_host(ports, channels, &_t), "sccsum_udp_ports_create_host");
+        detail::check(sccsum_udp_ports_create_host(ports, channels, _t.out()), "sccsum_udp_ports_create_host");
     }
-    udp_ports(const udp_ports&) = delete;
-    udp_ports& operator=(const udp_ports&) = delete;
-    ~udp_ports() { sccsum_udp_ports_destroy(_t); }
 
-    const sccsum_udp_ports* get() const noexcept { return _t; }
-    uint32_t channels() const noexcept { return sccsum_udp_ports_channels(_t); }
+    const sccsum_udp_ports* get() const noexcept { return _t.get(); }
+    uint32_t channels() const noexcept { return sccsum_udp_ports_channels(get()); }
 
     // host arithmetic: the channel bound to port, or -1
-    int lookup(uint16_t port) const noexcept { return sccsum_udp_ports_lookup(_t, port); }
+    int lookup(uint16_t port) const noexcept { return sccsum_udp_ports_lookup(get(), port); }
 };
 
 // UDP rx (<sccsum.h> sccsum_udp_rx / sccsum_udp_rx_reasm): the end of
@@ -724,12 +685,6 @@ public:
 class udp_rx {
     const udp_ports& _ports;
     uint32_t _host;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() / run_reassembled() write (device arrays; sizes in <sccsum.h>, "UDP layer")
@@ -771,19 +726,19 @@ public:
     void run(const device_packet_batch& ip, const uint8_t* d_status, const uint32_t* d_index, uint64_t n,
              const outputs& out, void* d_workspace, void* stream, uint32_t need = SCCSUM_ST_OK,
              uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE | SCCSUM_ST_IPFRAG) const {
-        check(sccsum_udp_rx(ip.bytes, ip.bytes_len, ip.off, ip.len, ip.n, d_status, need, reject, _host, _ports.get(),
-                            d_index, n, out.cls, out.first, out.order, out.pay_off, out.pay_len, out.src, out.sport,
-                            d_workspace, stream),
-              "sccsum_udp_rx");
+        detail::check(sccsum_udp_rx(ip.bytes, ip.bytes_len, ip.off, ip.len, ip.n, d_status, need, reject, _host,
+                                    _ports.get(), d_index, n, out.cls, out.first, out.order, out.pay_off, out.pay_len,
+                                    out.src, out.sport, d_workspace, stream),
+                      "sccsum_udp_rx");
     }
 
     // d_l4_status: what spans_desc wrote for the datagrams' L4 verify, or null (the masks then 0)
     void run_reassembled(const datagrams& in, const uint8_t* d_l4_status, const outputs& out, void* d_workspace,
                          void* stream, uint32_t need = 0, uint32_t reject = 0) const {
-        check(sccsum_udp_rx_reasm(in.desc, in.dgram_first, in.dgram_off, in.dgram_len, in.dgram_head, in.m, in.rec,
-                                  in.nrec, d_l4_status, need, reject, _host, _ports.get(), out.cls, out.first,
-                                  out.order, out.pay_len, out.src, out.sport, d_workspace, stream),
-              "sccsum_udp_rx_reasm");
+        detail::check(sccsum_udp_rx_reasm(in.desc, in.dgram_first, in.dgram_off, in.dgram_len, in.dgram_head, in.m,
+                                          in.rec, in.nrec, d_l4_status, need, reject, _host, _ports.get(), out.cls,
+                                          out.first, out.order, out.pay_len, out.src, out.sport, d_workspace, stream),
+                      "sccsum_udp_rx_reasm");
     }
 };
 
@@ -796,12 +751,6 @@ public:
 //   engine.sum_spans({d_bytes, bytes_len, out.l4_off, out.sum_len, n, 0}, out.seed, d_l4sum, ...);
 class udp_tx {
     sccsum_udp_opts _opts;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() writes (device arrays of n entries; <sccsum.h>, "UDP layer")
@@ -823,9 +772,9 @@ public:
     void run(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len, uint64_t n,
              const uint32_t* d_dst, const uint16_t* d_dport, const uint16_t* d_sport, const outputs& out,
              void* stream) const {
-        check(sccsum_udp_send(&_opts, d_bytes, bytes_len, d_off, d_len, d_dst, d_dport, d_sport, n, out.l4_off,
-                              out.l4_len, out.sum_len, out.seed, out.proto, out.needs_csum, out.status, stream),
-              "sccsum_udp_send");
+        detail::check(sccsum_udp_send(&_opts, d_bytes, bytes_len, d_off, d_len, d_dst, d_dport, d_sport, n, out.l4_off,
+                                      out.l4_len, out.sum_len, out.seed, out.proto, out.needs_csum, out.status, stream),
+                      "sccsum_udp_send");
     }
 };
 
@@ -838,36 +787,29 @@ public:
 //   const uint16_t listening[] = {80};
 //   tcp_conns conns(gpu, c, 1, listening, 1);
 class tcp_conns {
-    sccsum_tcp_conns* _t = nullptr;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
+    detail::handle<sccsum_tcp_conns, sccsum_tcp_conns_destroy> _t;
 
 public:
     // conns, listen: host memory, distinct, host order; nconns <= SCCSUM_TCP_MAX_CONNS, nlisten <= 65536
     tcp_conns(int device, const sccsum_tcp_conn* conns, uint32_t nconns, const uint16_t* listen, uint32_t nlisten) {
-        check(sccsum_tcp_conns_create(device, conns, nconns, listen, nlisten, &_t), "sccsum_tcp_conns_create");
+        detail::check(sccsum_tcp_conns_create(device, conns, nconns, listen, nlisten, _t.out()),
+                      "sccsum_tcp_conns_create");
     }
     // no device copy: lookup() and listening() alone
     tcp_conns(const sccsum_tcp_conn* conns, uint32_t nconns, const uint16_t* listen, uint32_t nlisten) {
-        check(sccsum_tcp_conns_create_host(conns, nconns, listen, nlisten, &_t), "sccsum_tcp_conns_create_host");
+        detail::check(sccsum_tcp_conns_create_host(conns, nconns, listen, nlisten, _t.out()),
+                      "sccsum_tcp_conns_create_host");
     }
-    tcp_conns(const tcp_conns&) = delete;
-    tcp_conns& operator=(const tcp_conns&) = delete;
-    ~tcp_conns() { sccsum_tcp_conns_destroy(_t); }
 
-    const sccsum_tcp_conns* get() const noexcept { return _t; }
-    uint32_t count() const noexcept { return sccsum_tcp_conns_count(_t); }
-    uint32_t bits() const noexcept { return sccsum_tcp_conns_bits(_t); }
+    const sccsum_tcp_conns* get() const noexcept { return _t.get(); }
+    uint32_t count() const noexcept { return sccsum_tcp_conns_count(get()); }
+    uint32_t bits() const noexcept { return sccsum_tcp_conns_bits(get()); }
 
     // host arithmetic: the connection of a connid, or -1; is the port listening
     int64_t lookup(const sccsum_tcp_conn& id) const noexcept {
-        return sccsum_tcp_conns_lookup(_t, id.local_ip, id.foreign_ip, id.local_port, id.foreign_port);
+        return sccsum_tcp_conns_lookup(get(), id.local_ip, id.foreign_ip, id.local_port, id.foreign_port);
     }
-    bool listening(uint16_t port) const noexcept { return sccsum_tcp_conns_listening(_t, port) != 0; }
+    bool listening(uint16_t port) const noexcept { return sccsum_tcp_conns_listening(get(), port) != 0; }
     // the home slot of a connid in a table of 2^bits slots
     static uint32_t slot(const sccsum_tcp_conn& id, uint32_t bits) noexcept {
         return sccsum_tcp_conns_slot(id.local_ip, id.foreign_ip, id.local_port, id.foreign_port, bits);
@@ -887,12 +829,6 @@ class tcp_rx {
     const tcp_conns& _conns;
     uint32_t _host;
     uint32_t _flags;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() writes (device arrays; sizes in <sccsum.h>, "TCP layer")
@@ -925,10 +861,10 @@ public:
     void run(const device_packet_batch& ip, const uint8_t* d_status, const uint32_t* d_index, uint64_t n,
              const outputs& out, void* d_workspace, void* stream, uint32_t need = SCCSUM_ST_OK | SCCSUM_ST_L4_OK,
              uint32_t reject = SCCSUM_ST_MALFORMED | SCCSUM_ST_RANGE | SCCSUM_ST_IPFRAG) const {
-        check(sccsum_tcp_rx(ip.bytes, ip.bytes_len, ip.off, ip.len, ip.n, d_status, need, reject, _host, _conns.get(),
-                            d_index, n, _flags, out.cls, out.first, out.order, out.seg, out.src, out.run_conn,
-                            out.run_first, out.rst, out.rst_dst, out.total, d_workspace, stream),
-              "sccsum_tcp_rx");
+        detail::check(sccsum_tcp_rx(ip.bytes, ip.bytes_len, ip.off, ip.len, ip.n, d_status, need, reject, _host,
+                                    _conns.get(), d_index, n, _flags, out.cls, out.first, out.order, out.seg, out.src,
+                                    out.run_conn, out.run_first, out.rst, out.rst_dst, out.total, d_workspace, stream),
+                      "sccsum_tcp_rx");
     }
 };
 
@@ -944,12 +880,6 @@ public:
 //   sccsum_gather(out.desc, total[0], d_stream_buf, stream);             // run r's bytes at [dst_off, + bytes)
 class tcp_rx_data {
     uint32_t _nconns;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() writes (device arrays; <sccsum.h>, "TCP receive fast path")
@@ -970,9 +900,9 @@ public:
     // its n; d_rcv: one sccsum_tcp_rcv per connection, 16-byte aligned; max_bytes <= 2^32 - 1
     void run(const void* d_bytes, const tcp_rx::outputs& rx, uint64_t n, const sccsum_tcp_rcv* d_rcv,
              uint64_t max_bytes, const outputs& out, void* d_workspace, void* stream) const {
-        check(sccsum_tcp_rx_data(d_bytes, rx.seg, rx.first, rx.run_conn, rx.run_first, rx.total, n, d_rcv, _nconns,
-                                 max_bytes, out.run, out.desc, out.total, d_workspace, stream),
-              "sccsum_tcp_rx_data");
+        detail::check(sccsum_tcp_rx_data(d_bytes, rx.seg, rx.first, rx.run_conn, rx.run_first, rx.total, n, d_rcv,
+                                         _nconns, max_bytes, out.run, out.desc, out.total, d_workspace, stream),
+                      "sccsum_tcp_rx_data");
     }
 };
 
@@ -985,12 +915,6 @@ public:
 //   engine.sum_spans({d_bytes, bytes_len, out.l4_off, out.sum_len, n, 0}, out.seed, d_l4sum, ...);
 class tcp_tx {
     sccsum_tcp_opts _opts;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() writes (device arrays of n entries; <sccsum.h>, "TCP layer")
@@ -1012,9 +936,10 @@ public:
     // d_bytes is written: the twenty fixed bytes at d_off - hdr_len of every accepted segment
     void run(void* d_bytes, uint64_t bytes_len, const uint64_t* d_off, const uint32_t* d_len,
              const sccsum_tcp_out* d_out, uint64_t n, const outputs& out, void* stream) const {
-        check(sccsum_tcp_send(&_opts, d_bytes, bytes_len, d_off, d_len, d_out, n, out.l4_off, out.l4_len, out.sum_len,
-                              out.seed, out.tso_seg, out.proto, out.needs_csum, out.status, stream),
-              "sccsum_tcp_send");
+        detail::check(sccsum_tcp_send(&_opts, d_bytes, bytes_len, d_off, d_len, d_out, n, out.l4_off, out.l4_len,
+                                      out.sum_len, out.seed, out.tso_seg, out.proto, out.needs_csum, out.status,
+                                      stream),
+                      "sccsum_tcp_send");
     }
 };
 
@@ -1030,12 +955,6 @@ public:
 //   tx.run(d_staging, total[1], out.off, out.len, out.out, total[0], tx_out, stream);
 class tcp_tx_data {
     sccsum_tcp_tx_opts _opts;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // the unsent queues as a CSR (device arrays): connection c's buffers are [first[c], first[c + 1])
@@ -1068,9 +987,10 @@ public:
     // d_snd: one sccsum_tcp_snd per polled connection, 16-byte aligned; max_segs <= 2^31 - 1, max_out_bytes <= 2^32 - 1
     void run(const sccsum_tcp_snd* d_snd, uint32_t nconns, const queues& q, uint64_t max_segs, uint64_t max_out_bytes,
              const outputs& out, void* d_workspace, void* stream) const {
-        check(sccsum_tcp_tx_data(&_opts, d_snd, nconns, q.src, q.len, q.first, q.nbuf, max_segs, max_out_bytes, out.run,
-                                 out.off, out.len, out.out, out.seg_first, out.desc, out.total, d_workspace, stream),
-              "sccsum_tcp_tx_data");
+        detail::check(sccsum_tcp_tx_data(&_opts, d_snd, nconns, q.src, q.len, q.first, q.nbuf, max_segs, max_out_bytes,
+                                         out.run, out.off, out.len, out.out, out.seg_first, out.desc, out.total,
+                                         d_workspace, stream),
+                      "sccsum_tcp_tx_data");
     }
 };
 
@@ -1085,12 +1005,6 @@ public:
 //   acks.run(rx_out, n, d_ack, queues, now_ns, out, d_ws, stream);   // rx_out: what tcp_rx::run wrote
 class tcp_rx_acks {
     uint32_t _nconns;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // the retransmit queues (_snd.data) as a CSR (device arrays): connection c's entries are [first[c], first[c + 1])
@@ -1119,9 +1033,10 @@ public:
     // connection, 16-byte aligned; now_ns: the one clock_type::now() of the batch
     void run(const tcp_rx::outputs& rx, uint64_t n, const sccsum_tcp_ack* d_ack, const queues& q, int64_t now_ns,
              const outputs& out, void* d_workspace, void* stream) const {
-        check(sccsum_tcp_rx_acks(rx.seg, rx.first, rx.run_conn, rx.run_first, rx.total, n, d_ack, _nconns, q.first, q.len,
-                                 q.meta, q.tx, q.nq, now_ns, out.run, out.total, d_workspace, stream),
-              "sccsum_tcp_rx_acks");
+        detail::check(sccsum_tcp_rx_acks(rx.seg, rx.first, rx.run_conn, rx.run_first, rx.total, n, d_ack, _nconns,
+                                         q.first, q.len, q.meta, q.tx, q.nq, now_ns, out.run, out.total, d_workspace,
+                                         stream),
+                      "sccsum_tcp_rx_acks");
     }
 };
 
@@ -1136,12 +1051,6 @@ public:
 //   tx.run(out.synack, 32 * total[1], out.sa_off, out.sa_len, out.sa_out, total[1], tx_out, stream);
 class tcp_listen {
     sccsum_tcp_listen_opts _opts;
-
-    static void check(int rc, const char* what) {
-        if (rc != SCCSUM_OK) {
-            throw std::runtime_error(std::string(what) + ": " + sccsum_strerror(rc));
-        }
-    }
 
 public:
     // what run() writes (device arrays with room for m_max entries; <sccsum.h>, "TCP passive open")
@@ -1169,10 +1078,10 @@ public:
     // the LISTEN bucket's size (tcp_rx's n always is one); d_space: 65536 words, the room left per listening port
     void run(const device_packet_batch& ip, const tcp_rx::outputs& rx, uint64_t m_max, const uint32_t* d_space,
              const outputs& out, void* d_workspace, void* stream) const {
-        check(sccsum_tcp_listen(_opts, ip.bytes, ip.bytes_len, ip.off, ip.n, rx.first, rx.order, rx.seg, rx.src, m_max,
-                                d_space, out.cls, out.rec, out.synack, out.sa_off, out.sa_len, out.sa_out, out.rst,
-                                out.rst_dst, out.total, d_workspace, stream),
-              "sccsum_tcp_listen");
+        detail::check(sccsum_tcp_listen(_opts, ip.bytes, ip.bytes_len, ip.off, ip.n, rx.first, rx.order, rx.seg, rx.src,
+                                        m_max, d_space, out.cls, out.rec, out.synack, out.sa_off, out.sa_len,
+                                        out.sa_out, out.rst, out.rst_dst, out.total, d_workspace, stream),
+                      "sccsum_tcp_listen");
     }
 };
 

@@ -511,7 +511,54 @@ def steer_dest(hash_value: int, ncpu: int, sw_reta, hw_queues: int | None = None
     return d
 
 
-class Steer:
+class _DeviceObject:
+    """What every object that owns a C-ABI handle does with it: `handle` for
+    the calls (an error once closed), close(), and a __del__ that stays quiet
+    at interpreter shutdown.  A subclass names its destroy call and itself as
+    error messages do, and once its create call has succeeded hands the handle
+    and its device to _own()."""
+    _destroy = ""   # the C-ABI call that frees the handle
+    _a = ""         # the class with its article: "an ArpTable"
+    _h = None
+    device = None   # torch.device, or None for a host-only table
+
+    def __init__(self):
+        self._lib = native.load()
+
+    def _own(self, h, device) -> None:
+        self._h = h
+        self.device = None if device is None else torch.device("cuda", int(device))
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError(f"{type(self).__name__} is closed")
+        return self._h
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            native.check(getattr(self._lib, self._destroy)(h), self._destroy)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def _device_handle(obj, cls, dev, what: str, optional: bool = False):
+    """The handle of a table of class `cls` for a call on data that lives on `dev`."""
+    if obj is None and optional:
+        return None
+    if not isinstance(obj, cls):
+        raise ValueError(f"{what}: need {cls._a}")
+    if obj.device != dev:
+        raise ValueError(f"{what}: the table lives on {obj.device}, the data on {dev}")
+    return obj.handle
+
+
+class Steer(_DeviceObject):
     """sccsum_steer_*: rx steering of a batch on the device (include/sccsum.h,
     "Rx steering"): every packet's destination shard from its RSS hash, and the
     batch's packet indices grouped by shard in arrival order.
@@ -523,19 +570,18 @@ class Steer:
     sw_reta is [hw_queues][128] (one row may be given flat); sw_reta_set marks
     the queues that have one (None: all).  The object is immutable and may be
     run from any thread on any stream of its device."""
+    _destroy, _a = "sccsum_steer_destroy", "a Steer"
 
     def __init__(self, ncpu: int, sw_reta, hw_queues: int | None = None, redir=None, table_bits: int = 0,
                  sw_reta_set=None, device: int = 0):
-        self._lib = native.load()
-        self._h = None
+        super().__init__()
         m, keep = _steer_map(ncpu, sw_reta, hw_queues, redir, table_bits, sw_reta_set)
         h = ctypes.c_void_p()
         native.check(self._lib.sccsum_steer_create(int(device), ctypes.addressof(m), ctypes.byref(h)),
                      "sccsum_steer_create")
         del keep
-        self._h = h
+        self._own(h, device)
         self.ncpu = int(ncpu)
-        self.device = torch.device("cuda", int(device))
 
     @staticmethod
     def check_args(dev, ncpu, hashes, status, need, reject, cpu, order, first) -> int:
@@ -562,8 +608,7 @@ class Steer:
         """(cpu uint8 [n], order int32 [n], first int32 [ncpu + 2]); cpu / order
         are None when want_cpu / want_order is False and no tensor was passed.
         Indices and counts are uint32 values in int32 tensors."""
-        if self._h is None:
-            raise ValueError("Steer is closed")
+        handle = self.handle
         dev = self.device
         n = self.check_args(dev, self.ncpu, hashes, status, need, reject, cpu, order, first)
         if cpu is None and want_cpu:
@@ -578,22 +623,11 @@ class Steer:
         _need(workspace, ws_bytes, torch.uint8, "workspace", dev)
         if n == 0:  # an empty tensor has no address: nothing to drop, only first is written
             status, need, reject = None, 0, 0
-        code = self._lib.sccsum_steer_run(self._h, int(mode), int(src_cpu), ctypes_ptr(hashes), _ptr(status),
+        code = self._lib.sccsum_steer_run(handle, int(mode), int(src_cpu), ctypes_ptr(hashes), _ptr(status),
                                           int(need), int(reject), n, _ptr(cpu), _ptr(order), ctypes_ptr(first),
                                           ctypes_ptr(workspace), _stream(stream))
         native.check(code, "sccsum_steer_run")
         return (None if cpu is None else cpu[:n]), (None if order is None else order[:n]), first[: self.ncpu + 2]
-
-    def close(self) -> None:
-        h, self._h = self._h, None
-        if h is not None:
-            native.check(self._lib.sccsum_steer_destroy(h), "sccsum_steer_destroy")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
 
 
 @dataclass
@@ -732,6 +766,12 @@ FRAG_NEED = native.ST_OK | native.ST_IPFRAG          # the fragments ip.cc:121-1
 FRAG_REJECT = native.ST_MALFORMED | native.ST_RANGE
 
 
+def _status_masks(need, reject) -> None:
+    for v, what in ((need, "need"), (reject, "reject")):
+        if not 0 <= int(v) <= 0xFF:
+            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+
+
 def frag_records_check(b: PacketBatch, status, need, reject, host_address, tag) -> int:
     """What frag_records refuses before any launch; returns n."""
     if not isinstance(b, PacketBatch):
@@ -742,9 +782,7 @@ def frag_records_check(b: PacketBatch, status, need, reject, host_address, tag) 
     if not isinstance(status, torch.Tensor) or status.dim() != 1:
         raise ValueError("status: need the 1-D uint8 tensor the frames call wrote, one entry per frame")
     _need(status, n, torch.uint8, "status", b.device)
-    for v, what in ((need, "need"), (reject, "reject")):
-        if not 0 <= int(v) <= 0xFF:
-            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+    _status_masks(need, reject)
     for v, what in ((host_address, "host_address"), (tag, "tag")):
         if not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError(f"{what}: need 0..2^32-1")
@@ -924,16 +962,16 @@ def mac_int(mac) -> int:
     return mac
 
 
-class ArpTable:
+class ArpTable(_DeviceObject):
     """sccsum_arp_table_*: an immutable copy of the stack's ARP table for the
     device calls below (include/sccsum.h, "Link layer").  `mapping` is a dict
     {ip: mac} or a sequence of (ip, mac) pairs, where a later pair for the same
     ip wins; ips in host order, macs as mac_int takes them.  device=None makes
     a host-only table (lookup alone).  A changed table is a new object."""
+    _destroy, _a = "sccsum_arp_table_destroy", "an ArpTable"
 
     def __init__(self, mapping=(), device: int | None = 0):
-        self._lib = native.load()
-        self._h = None
+        super().__init__()
         pairs = list(mapping.items()) if hasattr(mapping, "items") else list(mapping)
         if len(pairs) > native.ARP_MAX_ENTRIES:
             raise ValueError("mapping: at most 2^20 entries")
@@ -949,14 +987,7 @@ class ArpTable:
         else:
             code = self._lib.sccsum_arp_table_create(int(device), entries, len(pairs), ctypes.byref(h))
         native.check(code, "sccsum_arp_table_create")
-        self._h = h
-        self.device = None if device is None else torch.device("cuda", int(device))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise ValueError("ArpTable is closed")
-        return self._h
+        self._own(h, device)
 
     @property
     def bits(self) -> int:
@@ -968,30 +999,30 @@ class ArpTable:
         hit = self._lib.sccsum_arp_table_lookup(self.handle, int(ip) & 0xFFFFFFFF, ctypes.byref(mac))
         return int(mac.value) if hit else None
 
-    def close(self) -> None:
-        h, self._h = self._h, None
-        if h is not None:
-            native.check(self._lib.sccsum_arp_table_destroy(h), "sccsum_arp_table_destroy")
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
+class _Grouped:
+    """A result whose entries are grouped by bucket: `first` holds the bucket
+    bases, and the class names its buckets (_noun) and the tuple with one entry
+    per bucket that is not the dropped one (_keys)."""
+    _noun = ""
+    _keys = ""
 
+    def bounds(self) -> np.ndarray:
+        """first on the host (synchronises once)."""
+        if self._bounds is None:
+            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
+        return self._bounds
 
-def _device_table(table, dev, what: str, optional: bool = False):
-    if table is None and optional:
-        return None
-    if not isinstance(table, ArpTable):
-        raise ValueError(f"{what}: need an ArpTable")
-    if table.device != dev:
-        raise ValueError(f"{what}: the table lives on {table.device}, the data on {dev}")
-    return table.handle
+    def _range(self, k: int) -> tuple:
+        last = len(getattr(self, self._keys))
+        if not 0 <= int(k) <= last:
+            raise ValueError(f"{self._noun}: need 0..{last}")
+        b = self.bounds()
+        return int(b[k]), int(b[k + 1])
 
 
 @dataclass
-class EthRxResult:
+class EthRxResult(_Grouped):
     """What sccsum_eth_rx wrote (include/sccsum.h, "Link layer"): the batch's
     frames grouped by registered protocol, bucket len(protos) the dropped ones."""
     frames: PacketBatch       # the wire frames
@@ -1003,18 +1034,7 @@ class EthRxResult:
     src_mac_all: torch.Tensor  # int64 [n], grouped order (dropped: 0)
     cls: torch.Tensor | None  # uint8 [n], arrival order: k, or native.ETH_UNKNOWN / ETH_SHORT / ETH_RANGE
     _bounds: np.ndarray | None = None
-
-    def bounds(self) -> np.ndarray:
-        """first on the host (synchronises once)."""
-        if self._bounds is None:
-            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
-        return self._bounds
-
-    def _range(self, k: int) -> tuple:
-        if not 0 <= int(k) <= len(self.protos):
-            raise ValueError(f"bucket: need 0..{len(self.protos)}")
-        b = self.bounds()
-        return int(b[k]), int(b[k + 1])
+    _noun, _keys = "bucket", "protos"
 
     def bucket(self, k: int) -> PacketBatch:
         """Bucket k's frames behind their Ethernet header, a frames batch for
@@ -1098,14 +1118,11 @@ def arp_learn_check(b: PacketBatch, status, src_mac, host, netmask, table, need,
         if not isinstance(t, torch.Tensor) or t.dim() != 1:
             raise ValueError(f"{what}: need a 1-D {dtype} tensor of one entry per frame")
         _need(t, n, dtype, what, b.device)
-    for v, what in ((need, "need"), (reject, "reject")):
-        if not 0 <= int(v) <= 0xFF:
-            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+    _status_masks(need, reject)
     for v, what in ((host, "host"), (netmask, "netmask")):
         if not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError(f"{what}: need 0..2^32-1")
-    if table is not None:
-        _device_table(table, b.device, "table")
+    _device_handle(table, ArpTable, b.device, "table", optional=True)
     return n
 
 
@@ -1222,7 +1239,7 @@ def eth_send_check(lists, dst, dgram_first, table, hw_address, host, netmask, gw
         if not isinstance(dgram_first, torch.Tensor) or dgram_first.dim() != 1 or int(dgram_first.numel()) != n + 1:
             raise ValueError("dgram_first: need a 1-D int32 tensor of n + 1 entries")
         _need(dgram_first, n + 1, torch.int32, "dgram_first", dev)
-    _device_table(table, dev, "table")
+    _device_handle(table, ArpTable, dev, "table")
     mac_int(hw_address)
     for v, what in ((host, "host"), (netmask, "netmask"), (gw, "gw")):
         if not 0 <= int(v) <= 0xFFFFFFFF:
@@ -1292,15 +1309,15 @@ UDP_NEED = native.ST_OK                  # what ip.cc:121-144 lets through; the 
 UDP_REJECT = native.ST_MALFORMED | native.ST_RANGE | native.ST_IPFRAG
 
 
-class UdpPorts:
+class UdpPorts(_DeviceObject):
     """sccsum_udp_ports_*: the immutable port -> channel table of the UDP layer
     (include/sccsum.h, "UDP layer").  `ports` are distinct host-order ports,
     at most 252; channel k is ports[k].  device=None makes a host-only table
     (lookup alone).  A changed set of channels is a new object."""
+    _destroy, _a = "sccsum_udp_ports_destroy", "a UdpPorts"
 
     def __init__(self, ports=(), device: int | None = 0):
-        self._lib = native.load()
-        self._h = None
+        super().__init__()
         ports = tuple(int(p) for p in ports)
         if len(ports) > native.UDP_MAX_CHANNELS:
             raise ValueError("ports: at most 252 channels")
@@ -1314,15 +1331,8 @@ class UdpPorts:
         else:
             code = self._lib.sccsum_udp_ports_create(int(device), where, len(ports), ctypes.byref(h))
         native.check(code, "sccsum_udp_ports_create")
-        self._h = h
+        self._own(h, device)
         self.ports = ports
-        self.device = None if device is None else torch.device("cuda", int(device))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise ValueError("UdpPorts is closed")
-        return self._h
 
     @property
     def channels(self) -> int:
@@ -1333,28 +1343,9 @@ class UdpPorts:
         k = int(self._lib.sccsum_udp_ports_lookup(self.handle, int(port) & 0xFFFF))
         return None if k < 0 else k
 
-    def close(self) -> None:
-        h, self._h = self._h, None
-        if h is not None:
-            native.check(self._lib.sccsum_udp_ports_destroy(h), "sccsum_udp_ports_destroy")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-
-def _device_ports(ports, dev, what: str = "ports"):
-    if not isinstance(ports, UdpPorts):
-        raise ValueError(f"{what}: need a UdpPorts")
-    if ports.device != dev:
-        raise ValueError(f"{what}: the table lives on {ports.device}, the data on {dev}")
-    return ports.handle
-
 
 @dataclass
-class UdpRxResult:
+class UdpRxResult(_Grouped):
     """What sccsum_udp_rx / sccsum_udp_rx_reasm wrote (include/sccsum.h, "UDP
     layer"): the call's frames (datagrams) grouped by channel, bucket
     len(ports) everything dropped."""
@@ -1368,18 +1359,7 @@ class UdpRxResult:
     sport_all: torch.Tensor   # int16 [n], grouped order: the source port
     cls: torch.Tensor | None  # uint8 [n], arrival order: k, or native.UDP_SKIP / UDP_SHORT / UDP_NOPORT
     _bounds: np.ndarray | None = None
-
-    def bounds(self) -> np.ndarray:
-        """first on the host (synchronises once)."""
-        if self._bounds is None:
-            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
-        return self._bounds
-
-    def _range(self, k: int) -> tuple:
-        if not 0 <= int(k) <= len(self.ports):
-            raise ValueError(f"channel: need 0..{len(self.ports)}")
-        b = self.bounds()
-        return int(b[k]), int(b[k + 1])
+    _noun, _keys = "channel", "ports"
 
     def count(self, k: int) -> int:
         a, e = self._range(k)
@@ -1421,10 +1401,9 @@ class UdpRxResult:
         return self.sport_all[a:e]
 
 
-def _udp_masks(host, need, reject) -> None:
-    for v, what in ((need, "need"), (reject, "reject")):
-        if not 0 <= int(v) <= 0xFF:
-            raise ValueError(f"{what}: need a mask of status bits, 0..0xFF")
+def _rx_filter(host, need, reject) -> None:
+    """What the UDP and TCP rx calls take of a frame: the status masks and the host address."""
+    _status_masks(need, reject)
     if not 0 <= int(host) <= 0xFFFFFFFF:
         raise ValueError("host: need a host-order IPv4 address, 0..2^32-1")
 
@@ -1439,7 +1418,7 @@ def udp_rx_check(b: PacketBatch, status, ports, host, need, reject, index=None, 
     if not isinstance(status, torch.Tensor) or status.dim() != 1:
         raise ValueError("status: need the 1-D uint8 tensor the frames call wrote, one entry per frame")
     _need(status, nbatch, torch.uint8, "status", b.device)
-    _udp_masks(host, need, reject)
+    _rx_filter(host, need, reject)
     n = nbatch
     if index is not None:
         if not isinstance(index, torch.Tensor) or index.dim() != 1:
@@ -1451,7 +1430,7 @@ def udp_rx_check(b: PacketBatch, status, ports, host, need, reject, index=None, 
     if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
         raise ValueError("cls: need a 1-D uint8 tensor of one entry per frame")
     _need(cls, n, torch.uint8, "cls", b.device)
-    _device_ports(ports, b.device)
+    _device_handle(ports, UdpPorts, b.device, "ports")
     return n, nbatch
 
 
@@ -1508,7 +1487,7 @@ def udp_rx_reasm_check(r, records, ports, host, l4_status, need, reject, cls=Non
     nrec = reasm_check(records, None, 0)
     dev = records.device
     m = r.totals()[0]
-    _udp_masks(host, need, reject)
+    _rx_filter(host, need, reject)
     if l4_status is None:
         if int(need) or int(reject):
             raise ValueError("need / reject: masks need l4_status")
@@ -1519,7 +1498,7 @@ def udp_rx_reasm_check(r, records, ports, host, l4_status, need, reject, cls=Non
     if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
         raise ValueError("cls: need a 1-D uint8 tensor of one entry per datagram")
     _need(cls, m, torch.uint8, "cls", dev)
-    _device_ports(ports, dev)
+    _device_handle(ports, UdpPorts, dev, "ports")
     return m, nrec
 
 
@@ -1638,17 +1617,17 @@ TCP_OUT_DTYPE = np.dtype([("dst", "<u4"), ("seq", "<u4"), ("ack", "<u4"), ("spor
                           ("window", "<u2"), ("flags", "u1"), ("hdr_len", "u1"), ("mss", "<u4")])
 
 
-class TcpConns:
+class TcpConns(_DeviceObject):
     """sccsum_tcp_conns_*: the immutable connection table of the TCP layer
     (include/sccsum.h, "TCP layer").  `conns` are distinct (local_ip,
     foreign_ip, local_port, foreign_port) in host order, at most 2^20;
     connection c is conns[c].  `listen` are the distinct listening ports.
     device=None makes a host-only table (lookup alone).  A changed set of
     connections is a new object."""
+    _destroy, _a = "sccsum_tcp_conns_destroy", "a TcpConns"
 
     def __init__(self, conns=(), listen=(), device: int | None = 0):
-        self._lib = native.load()
-        self._h = None
+        super().__init__()
         arr = np.asarray(conns, dtype=np.int64).reshape(-1, 4)
         listen = np.asarray(listen, dtype=np.int64).reshape(-1)
         if arr.shape[0] > native.TCP_MAX_CONNS:
@@ -1676,15 +1655,8 @@ class TcpConns:
         if code == native.SCCSUM_EINVAL:
             raise ValueError("conns: a connection given twice")
         native.check(code, "sccsum_tcp_conns_create")
-        self._h = h
+        self._own(h, device)
         self.nconns = int(arr.shape[0])
-        self.device = None if device is None else torch.device("cuda", int(device))
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise ValueError("TcpConns is closed")
-        return self._h
 
     @property
     def count(self) -> int:
@@ -1703,20 +1675,9 @@ class TcpConns:
     def listening(self, port: int) -> bool:
         return bool(self._lib.sccsum_tcp_conns_listening(self.handle, int(port) & 0xFFFF))
 
-    def close(self) -> None:
-        h, self._h = self._h, None
-        if h is not None:
-            native.check(self._lib.sccsum_tcp_conns_destroy(h), "sccsum_tcp_conns_destroy")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
 
 @dataclass
-class TcpRxResult:
+class TcpRxResult(_Grouped):   # bounds() alone: its four buckets have no names to range over
     """What sccsum_tcp_rx wrote (include/sccsum.h, "TCP layer"): the call's
     segments grouped by bucket (0 a known connection, 1 a listening port, 2
     answered with a RST, 3 dropped), bucket 0 by connection."""
@@ -1733,12 +1694,6 @@ class TcpRxResult:
     cls: torch.Tensor | None  # uint8 [n], arrival order: native.TCP_*
     _bounds: np.ndarray | None = None
     _totals: tuple | None = None
-
-    def bounds(self) -> np.ndarray:
-        """first on the host (synchronises once)."""
-        if self._bounds is None:
-            self._bounds = self.first.cpu().numpy().view(np.uint32).astype(np.int64)
-        return self._bounds
 
     def totals(self) -> tuple:
         """(R, resets) on the host (synchronises once)."""
@@ -1791,7 +1746,7 @@ def tcp_rx_check(b: PacketBatch, status, conns, host, need, reject, index=None, 
     if not isinstance(status, torch.Tensor) or status.dim() != 1:
         raise ValueError("status: need the 1-D uint8 tensor the frames call wrote, one entry per frame")
     _need(status, nbatch, torch.uint8, "status", b.device)
-    _udp_masks(host, need, reject)
+    _rx_filter(host, need, reject)
     if int(flags) & ~native.TCP_CSUM_OFFLOAD:
         raise ValueError(f"flags: unknown bits in {int(flags):#x}")
     n = nbatch
@@ -1805,8 +1760,9 @@ def tcp_rx_check(b: PacketBatch, status, conns, host, need, reject, index=None, 
     if cls is not None and (not isinstance(cls, torch.Tensor) or cls.dim() != 1):
         raise ValueError("cls: need a 1-D uint8 tensor of one entry per frame")
     _need(cls, n, torch.uint8, "cls", b.device)
+    # not _device_handle: the check never asked for the handle, so a closed table is tcp_rx's to refuse
     if not isinstance(conns, TcpConns):
-        raise ValueError("conns: need a TcpConns")
+        raise ValueError(f"conns: need {TcpConns._a}")
     if conns.device != b.device:
         raise ValueError(f"conns: the table lives on {conns.device}, the data on {b.device}")
     return n, nbatch
@@ -1865,8 +1821,40 @@ TCP_RCV_RUN_DTYPE = np.dtype([("taken", "<u4"), ("bytes", "<u4"), ("next", "<u4"
                               ("pad", "<u2")])
 
 
+class _RunRecords:
+    """A result with one record per run (or polled connection) in `run` and
+    its counts in `total`: both on the host, fetched once.  The classes keep
+    totals() and runs_host() themselves, for what their docstrings say."""
+
+    def _totals_host(self) -> tuple:
+        if self._totals is None:
+            self._totals = tuple(int(x) for x in self.total.cpu().numpy().view(np.uint64))
+        return self._totals
+
+    def _runs_host(self, dtype) -> np.ndarray:
+        if self._runs is None:
+            self._runs = self.runs.cpu().numpy().reshape(-1).view(dtype)
+        return self._runs
+
+
+class _RxRunRecords(_RunRecords):
+    """The run records of a fast path over tcp_rx's bucket 0 (`rx`): one per
+    run of rx, the first `taken` segments of each dealt with."""
+
+    @property
+    def runs(self) -> torch.Tensor:
+        """The R run records (a view)."""
+        return self.run[:self.rx.totals()[0]]
+
+    def rest(self, conn_run: int) -> torch.Tensor:
+        """The records of run conn_run the host still has to walk with its
+        tcb, from the state in the run record: segs(conn_run)[taken:]."""
+        segs = self.rx.segs(conn_run)
+        return segs[int(self.runs_host()["taken"][int(conn_run)]):]
+
+
 @dataclass
-class TcpRxDataResult:
+class TcpRxDataResult(_RxRunRecords):
     """What sccsum_tcp_rx_data wrote (include/sccsum.h, "TCP receive fast
     path"): the leading in-sequence stretch of every run of tcp_rx's bucket 0."""
     rx: TcpRxResult
@@ -1878,21 +1866,14 @@ class TcpRxDataResult:
 
     def totals(self) -> tuple:
         """(taken, bytes, needed) on the host (synchronises once)."""
-        if self._totals is None:
+        if self._totals is None:   # not _totals_host: three of the four words, read as the int64 they are
             t = self.total.cpu().numpy()
             self._totals = (int(t[0]), int(t[1]), int(t[2]))
         return self._totals
 
-    @property
-    def runs(self) -> torch.Tensor:
-        """The R run records (a view)."""
-        return self.run[:self.rx.totals()[0]]
-
     def runs_host(self) -> np.ndarray:
         """The run records on the host as TCP_RCV_RUN_DTYPE (synchronises once)."""
-        if self._runs is None:
-            self._runs = self.runs.cpu().numpy().reshape(-1).view(TCP_RCV_RUN_DTYPE)
-        return self._runs
+        return self._runs_host(TCP_RCV_RUN_DTYPE)
 
     @property
     def descs(self) -> torch.Tensor:
@@ -1909,11 +1890,32 @@ class TcpRxDataResult:
                          "sccsum_gather")
         return data
 
-    def rest(self, conn_run: int) -> torch.Tensor:
-        """The records of run conn_run the host still has to walk with its
-        tcb, from the state in the run record: segs(conn_run)[taken:]."""
-        segs = self.rx.segs(conn_run)
-        return segs[int(self.runs_host()["taken"][int(conn_run)]):]
+
+def _conn_records(t, width: int, name: str, struct: str, dev=None, rx=None) -> int:
+    """A fast path's per-connection state: a uint8 [nconns, width] tensor of
+    sccsum_tcp_<struct> records on `dev` (its own device when None), 16-byte
+    aligned; with `rx`, for no more connections than tcp_rx's table had.
+    Returns nconns."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"{name}: need a uint8 [nconns, {width}] tensor of sccsum_tcp_{struct} records "
+                         f"(TCP_{struct.upper()}_DTYPE)")
+    nconns = int(t.shape[0])
+    if nconns > native.TCP_MAX_CONNS:
+        raise ValueError(f"{name}: at most 2^20 connections")
+    _need(t, width * nconns, torch.uint8, name, t.device if dev is None else dev)
+    if nconns and t.data_ptr() % 16:
+        raise ValueError(f"{name}: need a 16-byte aligned tensor")
+    if rx is not None and int(rx.run_conn.numel()) < min(int(rx.seg.shape[0]), nconns) + 1:
+        raise ValueError(f"{name}: {nconns} connections, but rx was made with a table of fewer")
+    return nconns
+
+
+def _flat_tensors(dev, *named) -> None:
+    """Every (name, tensor, dtype) is a contiguous 1-D tensor of that dtype on dev."""
+    for what, t, dtype in named:
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f"{what}: need a 1-D {dtype} tensor")
+        _need(t, t.numel(), dtype, what, dev)
 
 
 def tcp_rx_data_check(rx, rcv, max_bytes) -> tuple:
@@ -1922,16 +1924,7 @@ def tcp_rx_data_check(rx, rcv, max_bytes) -> tuple:
         raise ValueError("rx: need the TcpRxResult of tcp_rx")
     dev = rx.seg.device
     n = int(rx.seg.shape[0])
-    if not isinstance(rcv, torch.Tensor) or rcv.dim() != 2 or rcv.shape[1] != 32:
-        raise ValueError("rcv: need a uint8 [nconns, 32] tensor of sccsum_tcp_rcv records (TCP_RCV_DTYPE)")
-    nconns = int(rcv.shape[0])
-    if nconns > native.TCP_MAX_CONNS:
-        raise ValueError("rcv: at most 2^20 connections")
-    _need(rcv, 32 * nconns, torch.uint8, "rcv", dev)
-    if nconns and rcv.data_ptr() % 16:
-        raise ValueError("rcv: need a 16-byte aligned tensor")
-    if int(rx.run_conn.numel()) < min(n, nconns) + 1:
-        raise ValueError(f"rcv: {nconns} connections, but rx was made with a table of fewer")
+    nconns = _conn_records(rcv, 32, "rcv", "rcv", dev, rx)
     if not 0 <= int(max_bytes) <= 0xFFFFFFFF:
         raise ValueError("max_bytes: need 0..2^32-1")
     return n, nconns
@@ -2053,7 +2046,7 @@ TCP_SND_RUN_DTYPE = np.dtype([("segs", "<u4"), ("bytes", "<u4"), ("seg_first", "
 
 
 @dataclass
-class TcpTxDataResult:
+class TcpTxDataResult(_RunRecords):   # no rx behind it: every record is a polled connection's
     """What sccsum_tcp_tx_data wrote (include/sccsum.h, "TCP transmit fast
     path"): every polled connection's unsent queue cut into segments."""
     run: torch.Tensor          # uint8 [P, 32]: sccsum_tcp_snd_run records (TCP_SND_RUN_DTYPE on the host)
@@ -2069,20 +2062,16 @@ class TcpTxDataResult:
 
     def totals(self) -> tuple:
         """(segments, layout bytes, descriptors, layout bytes needed) on the host (synchronises once)."""
-        if self._totals is None:
-            self._totals = tuple(int(x) for x in self.total.cpu().numpy().view(np.uint64))
-        return self._totals
+        return self._totals_host()
+
+    def runs_host(self) -> np.ndarray:
+        """The run records on the host as TCP_SND_RUN_DTYPE (synchronises once)."""
+        return self._runs_host(TCP_SND_RUN_DTYPE)
 
     @property
     def runs(self) -> torch.Tensor:
         """The P run records (a view)."""
         return self.run
-
-    def runs_host(self) -> np.ndarray:
-        """The run records on the host as TCP_SND_RUN_DTYPE (synchronises once)."""
-        if self._runs is None:
-            self._runs = self.run.cpu().numpy().reshape(-1).view(TCP_SND_RUN_DTYPE)
-        return self._runs
 
     @property
     def descs(self) -> torch.Tensor:
@@ -2113,20 +2102,9 @@ class TcpTxDataResult:
 def tcp_tx_data_check(snd, buf_src, buf_len, buf_first, src_host, mtu, headroom, flags, max_packet_len, max_segs,
                       max_out_bytes) -> tuple:
     """What tcp_tx_data refuses before any launch; returns (nconns, nbuf)."""
-    if not isinstance(snd, torch.Tensor) or snd.dim() != 2 or snd.shape[1] != 48:
-        raise ValueError("snd: need a uint8 [nconns, 48] tensor of sccsum_tcp_snd records (TCP_SND_DTYPE)")
-    dev = snd.device
-    nconns = int(snd.shape[0])
-    if nconns > native.TCP_MAX_CONNS:
-        raise ValueError("snd: at most 2^20 connections")
-    _need(snd, 48 * nconns, torch.uint8, "snd", dev)
-    if nconns and snd.data_ptr() % 16:
-        raise ValueError("snd: need a 16-byte aligned tensor")
-    for what, t, dtype in (("buf_src", buf_src, torch.int64), ("buf_len", buf_len, torch.int32),
-                           ("buf_first", buf_first, torch.int32)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 1:
-            raise ValueError(f"{what}: need a 1-D {dtype} tensor")
-        _need(t, t.numel(), dtype, what, dev)
+    nconns = _conn_records(snd, 48, "snd", "snd")
+    _flat_tensors(snd.device, ("buf_src", buf_src, torch.int64), ("buf_len", buf_len, torch.int32),
+                  ("buf_first", buf_first, torch.int32))
     nbuf = int(buf_src.numel())
     if int(buf_len.numel()) != nbuf:
         raise ValueError("buf_len: need one length per buffer address")
@@ -2216,7 +2194,7 @@ class TcpAckQueues:
 
 
 @dataclass
-class TcpRxAcksResult:
+class TcpRxAcksResult(_RxRunRecords):
     """What sccsum_tcp_rx_acks wrote (include/sccsum.h, "TCP ACK fast path"):
     the leading stretch of advancing pure ACKs of every run of tcp_rx's bucket 0."""
     rx: TcpRxResult
@@ -2227,26 +2205,11 @@ class TcpRxAcksResult:
 
     def totals(self) -> tuple:
         """(R, taken, popped, acked) on the host (synchronises once)."""
-        if self._totals is None:
-            self._totals = tuple(int(x) for x in self.total.cpu().numpy().view(np.uint64))
-        return self._totals
-
-    @property
-    def runs(self) -> torch.Tensor:
-        """The R run records (a view)."""
-        return self.run[:self.rx.totals()[0]]
+        return self._totals_host()
 
     def runs_host(self) -> np.ndarray:
         """The run records on the host as TCP_ACK_RUN_DTYPE (synchronises once)."""
-        if self._runs is None:
-            self._runs = self.runs.cpu().numpy().reshape(-1).view(TCP_ACK_RUN_DTYPE)
-        return self._runs
-
-    def rest(self, conn_run: int) -> torch.Tensor:
-        """The records of run conn_run the host still has to walk with its
-        tcb, from the state in the run record: segs(conn_run)[taken:]."""
-        segs = self.rx.segs(conn_run)
-        return segs[int(self.runs_host()["taken"][int(conn_run)]):]
+        return self._runs_host(TCP_ACK_RUN_DTYPE)
 
 
 def tcp_rx_acks_check(rx, ack_state, queue, now_ns) -> tuple:
@@ -2255,23 +2218,11 @@ def tcp_rx_acks_check(rx, ack_state, queue, now_ns) -> tuple:
         raise ValueError("rx: need the TcpRxResult of tcp_rx")
     dev = rx.seg.device
     n = int(rx.seg.shape[0])
-    if not isinstance(ack_state, torch.Tensor) or ack_state.dim() != 2 or ack_state.shape[1] != 64:
-        raise ValueError("ack_state: need a uint8 [nconns, 64] tensor of sccsum_tcp_ack records (TCP_ACK_DTYPE)")
-    nconns = int(ack_state.shape[0])
-    if nconns > native.TCP_MAX_CONNS:
-        raise ValueError("ack_state: at most 2^20 connections")
-    _need(ack_state, 64 * nconns, torch.uint8, "ack_state", dev)
-    if nconns and ack_state.data_ptr() % 16:
-        raise ValueError("ack_state: need a 16-byte aligned tensor")
-    if int(rx.run_conn.numel()) < min(n, nconns) + 1:
-        raise ValueError(f"ack_state: {nconns} connections, but rx was made with a table of fewer")
+    nconns = _conn_records(ack_state, 64, "ack_state", "ack", dev, rx)
     if not isinstance(queue, TcpAckQueues):
         raise ValueError("queue: need a TcpAckQueues")
-    for what, t, dtype in (("queue.first", queue.first, torch.int32), ("queue.length", queue.length, torch.int32),
-                           ("queue.meta", queue.meta, torch.int32), ("queue.tx", queue.tx, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 1:
-            raise ValueError(f"{what}: need a 1-D {dtype} tensor")
-        _need(t, t.numel(), dtype, what, dev)
+    _flat_tensors(dev, ("queue.first", queue.first, torch.int32), ("queue.length", queue.length, torch.int32),
+                  ("queue.meta", queue.meta, torch.int32), ("queue.tx", queue.tx, torch.int64))
     nq = int(queue.length.numel())
     if nq > native.TCP_ACK_MAX_ENTRIES:
         raise ValueError("queue.length: at most 2^31 entries")

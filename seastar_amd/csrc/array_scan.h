@@ -71,17 +71,13 @@ static __global__ __launch_bounds__(kBlock) void scan_place(Load L, uint64_t n, 
 // out[0 .. n] = the exclusive scan of L over [0, n) and its sum; `tsum` is one V per tile.
 template <typename V, typename Load>
 static inline hipError_t scan_array(hipStream_t st, const Load& L, uint64_t n, V* tsum, V* out) {
-    using host_launch::launch_kernel;
     const uint64_t ntiles = wire::tiles_of(n, kTile);
     const dim3 tiles(static_cast<unsigned>(ntiles)), block(kBlock);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(scan_tile<V, Load>, tiles, block, 0, st, L, n, tsum);
-        if (e != hipSuccess) return e;
-    }
-    e = launch_kernel(scan_carry<V>, dim3(1), block, 0, st, tsum, ntiles, out + n);
-    if (e != hipSuccess || !ntiles) return e;
-    return launch_kernel(scan_place<V, Load>, tiles, block, 0, st, L, n, static_cast<const V*>(tsum), out);
+    host_launch::Chain c{st};
+    if (ntiles) c.launch(scan_tile<V, Load>, tiles, block, 0, L, n, tsum);
+    c.launch(scan_carry<V>, dim3(1), block, 0, tsum, ntiles, out + n);
+    if (ntiles) c.launch(scan_place<V, Load>, tiles, block, 0, L, n, tsum, out);
+    return c.e;
 }
 
 }  // namespace array_scan

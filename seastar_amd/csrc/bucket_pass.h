@@ -152,18 +152,16 @@ static __global__ __launch_bounds__(kBlock) void scan_totals_kernel(const uint32
 template <int kBlock, int kMaxBuckets>
 static inline hipError_t scan_buckets(hipStream_t st, uint32_t* ws, uint32_t ntiles, uint32_t pitch, uint32_t buckets,
                                       uint32_t* d_first, uint32_t* totals) {
-    using host_launch::launch_kernel;
+    host_launch::Chain c{st};
     if constexpr (kMaxBuckets > kScanOneBlockMax) {
         if (buckets > kScanOneBlockMax && ntiles != 0) {
-            const hipError_t e =
-                launch_kernel(scan_rows_kernel<>, dim3(buckets), dim3(kWave), 0, st, ws, ntiles, pitch, totals);
-            if (e != hipSuccess) return e;
-            return launch_kernel(scan_totals_kernel<>, dim3(1), dim3(kWave), 0, st, static_cast<const uint32_t*>(totals),
-                                 buckets, d_first);
+            c.launch(scan_rows_kernel<>, dim3(buckets), dim3(kWave), 0, ws, ntiles, pitch, totals);
+            c.launch(scan_totals_kernel<>, dim3(1), dim3(kWave), 0, totals, buckets, d_first);
+            return c.e;
         }
     }
-    return launch_kernel(scan_kernel<kBlock, kMaxBuckets>, dim3(1), dim3(kBlock), 0, st, ws, ntiles, pitch, buckets,
-                         d_first);
+    c.launch(scan_kernel<kBlock, kMaxBuckets>, dim3(1), dim3(kBlock), 0, ws, ntiles, pitch, buckets, d_first);
+    return c.e;
 }
 
 // ---------------------------------------------------------------- scatter

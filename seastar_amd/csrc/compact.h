@@ -68,16 +68,12 @@ static __global__ __launch_bounds__(kBlock) void place_kernel(Pred P, const uint
 template <int kBlock, typename Pred>
 static inline hipError_t run(hipStream_t st, const Pred& P, uint64_t ntiles, uint32_t* tcount, uint32_t* d_count,
                              typename Pred::Out* d_out) {
-    using host_launch::launch_kernel;
     const dim3 tiles(static_cast<unsigned>(ntiles)), block(kBlock);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(tile_kernel<kBlock, Pred>, tiles, block, 0, st, P, tcount);
-        if (e != hipSuccess) return e;
-    }
-    e = launch_kernel(carry_kernel<kBlock>, dim3(1), block, 0, st, tcount, ntiles, d_count);
-    if (e != hipSuccess || !ntiles) return e;
-    return launch_kernel(place_kernel<kBlock, Pred>, tiles, block, 0, st, P, static_cast<const uint32_t*>(tcount), d_out);
+    host_launch::Chain c{st};
+    if (ntiles) c.launch(tile_kernel<kBlock, Pred>, tiles, block, 0, P, tcount);
+    c.launch(carry_kernel<kBlock>, dim3(1), block, 0, tcount, ntiles, d_count);
+    if (ntiles) c.launch(place_kernel<kBlock, Pred>, tiles, block, 0, P, tcount, d_out);
+    return c.e;
 }
 
 }  // namespace compact

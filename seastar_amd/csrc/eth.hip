@@ -46,13 +46,14 @@
 namespace eth {
 
 using bucket_pass::pitch_of;
-using host_launch::launch_kernel;
+using host_launch::Chain;
+using host_launch::device_ok;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::upload;
 using wave_scan::block_inclusive_scan;
 using wire::fmix32;
 using wire::kIpHdrMin;
-using wire::kMaxDevices;
 using wire::tiles_of;
 
 constexpr int kWave = 64;
@@ -524,31 +525,18 @@ int sccsum_arp_table_create(int device, const sccsum_arp_entry* entries, uint32_
     if (!out) return SCCSUM_EINVAL;
     *out = nullptr;
     if (!entries_ok(entries, n)) return SCCSUM_EINVAL;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess) return e == hipErrorNoDevice ? SCCSUM_ENODEV : static_cast<int>(e);
-    if (device < 0 || device >= ndev || device >= kMaxDevices) return SCCSUM_ENODEV;
-    sccsum_arp_table* t = nullptr;
-    const int rc = new_table(entries, n, &t);
+    int rc = device_ok(device);
     if (rc != SCCSUM_OK) return rc;
-    int cur = 0;
-    e = hipGetDevice(&cur);
-    if (e == hipSuccess) e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        void* d = nullptr;
-        const size_t bytes = t->slots.size() * sizeof(Slot);
-        e = hipMalloc(&d, bytes);
-        if (e == hipSuccess) {
-            t->d_slots = static_cast<Slot*>(d);
-            e = hipMemcpy(d, t->slots.data(), bytes, hipMemcpyHostToDevice);
-        }
-        (void)hipSetDevice(cur);  // the caller's binding is put back
-    }
-    if (e != hipSuccess) {
-        if (t->d_slots) (void)hipFree(t->d_slots);
+    sccsum_arp_table* t = nullptr;
+    rc = new_table(entries, n, &t);
+    if (rc != SCCSUM_OK) return rc;
+    void* d[1];
+    rc = upload(device, {{t->slots.data(), t->slots.size() * sizeof(Slot)}}, d);
+    if (rc != SCCSUM_OK) {
         delete t;
-        return static_cast<int>(e);
+        return rc;
     }
+    t->d_slots = static_cast<Slot*>(d[0]);
     t->device = device;
     *out = t;
     return SCCSUM_OK;
@@ -556,7 +544,7 @@ int sccsum_arp_table_create(int device, const sccsum_arp_entry* entries, uint32_
 
 int sccsum_arp_table_destroy(sccsum_arp_table* t) {
     if (!t) return SCCSUM_OK;
-    const hipError_t e = t->d_slots ? hipFree(t->d_slots) : hipSuccess;
+    const hipError_t e = host_launch::free_all({t->d_slots});
     delete t;
     return static_cast<int>(e);
 }
@@ -609,18 +597,15 @@ int sccsum_eth_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off
     const uint32_t ntiles = static_cast<uint32_t>(tiles_of(n, kTile));
     const uint32_t pitch = pitch_of(ntiles);
     uint32_t* const ws = static_cast<uint32_t*>(d_workspace);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(eth_rx_count_kernel, dim3(ntiles), dim3(kBlock), 0, st, F, P, d_class, ws, pitch);
-        if (e != hipSuccess) return static_cast<int>(e);
-    }
+    Chain c{st};
+    if (ntiles) c.launch(eth_rx_count_kernel, dim3(ntiles), dim3(kBlock), 0, F, P, d_class, ws, pitch);
     // at most nine buckets: always the one-block scan, which leaves no totals behind the rows
     static_assert(kMaxBuckets <= bucket_pass::kScanOneBlockMax, "sccsum_eth_rx_workspace has no room for totals");
-    e = bucket_pass::scan_buckets<kBlock, kMaxBuckets>(st, ws, ntiles, pitch, nprotos + 1u, d_first, nullptr);
-    if (e != hipSuccess || !ntiles) return static_cast<int>(e);
-    e = launch_kernel(eth_rx_scatter_kernel, dim3(ntiles), dim3(kBlock), 0, st, F, P, static_cast<const uint32_t*>(ws),
-                      pitch, static_cast<const uint32_t*>(d_first), d_order, d_l3_off, d_l3_len, d_src_mac);
-    return static_cast<int>(e);
+    if (c.ok()) c.e = bucket_pass::scan_buckets<kBlock, kMaxBuckets>(st, ws, ntiles, pitch, nprotos + 1u, d_first, nullptr);
+    if (!ntiles) return c.rc();
+    c.launch(eth_rx_scatter_kernel, dim3(ntiles), dim3(kBlock), 0, F, P, ws, pitch, d_first, d_order, d_l3_off, d_l3_len,
+             d_src_mac);
+    return c.rc();
 }
 
 uint64_t sccsum_arp_learn_workspace(uint64_t n) {
@@ -696,21 +681,16 @@ int sccsum_eth_send(const sccsum_eth_opts* opts, const sccsum_arp_table* table, 
     const SendOut O{d_eth, d_desc_out, d_first_out, d_off_out, d_len_out, d_frame_src, d_status, d_unresolved};
     const uint64_t ntiles = tiles_of(n, kTile);
     uint64_t* const ws = static_cast<uint64_t*>(d_workspace);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(eth_send_count_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, st, S, ws);
-        if (e != hipSuccess) return static_cast<int>(e);
-    }
-    e = launch_kernel(eth_send_scan_kernel, dim3(1), dim3(kBlock), 0, st, S, ws, ntiles, max_out_bytes, d_first_out,
-                      d_total);
-    if (e != hipSuccess || !ntiles) return static_cast<int>(e);
-    e = launch_kernel(eth_send_place_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kBlock), 0, st, S,
-                      static_cast<const uint64_t*>(ws), opts->hw_address, uint32_t(opts->eth_proto), O);
-    if (e != hipSuccess || !nframes) return static_cast<int>(e);
+    const dim3 tiles(static_cast<unsigned>(ntiles)), block(kBlock);
+    Chain c{st};
+    if (ntiles) c.launch(eth_send_count_kernel, tiles, block, 0, S, ws);
+    c.launch(eth_send_scan_kernel, dim3(1), block, 0, S, ws, ntiles, max_out_bytes, d_first_out, d_total);
+    if (!ntiles) return c.rc();
+    c.launch(eth_send_place_kernel, tiles, block, 0, S, ws, opts->hw_address, uint32_t(opts->eth_proto), O);
+    if (!nframes) return c.rc();
     const uint64_t blocks = std::min<uint64_t>((nframes + kEmitBlock - 1) / kEmitBlock, kEmitMaxBlocks);
-    e = launch_kernel(eth_send_emit_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kEmitBlock), 0, st, S,
-                      static_cast<const uint64_t*>(ws), O);
-    return static_cast<int>(e);
+    c.launch(eth_send_emit_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kEmitBlock), 0, S, ws, O);
+    return c.rc();
 }
 
 }  // extern "C"

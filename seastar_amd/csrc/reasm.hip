@@ -46,9 +46,10 @@ namespace reasm {
 
 using bucket_pass::kDigits;
 using bucket_pass::scan_rows_kernel;
-using host_launch::launch_kernel;
+using host_launch::Chain;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::Workspace;
 using wave_scan::block_inclusive_scan;
 using wire::be32_at;
 using wire::fmix32;
@@ -648,35 +649,30 @@ struct Layout {
 
 Layout layout(uint64_t m) {
     Layout L{};
-    uint64_t at = 0;
-    auto take = [&](uint64_t bytes) {
-        const uint64_t here = at;
-        at += (bytes + 15) & ~uint64_t(15);
-        return here;
-    };
+    host_launch::Carver c;
     L.sort_tiles = static_cast<uint32_t>(tiles_of(m, kSortTile));
     L.pitch = bucket_pass::pitch_of(L.sort_tiles);
     L.scan_tiles = static_cast<uint32_t>(tiles_of(m, kScanTile));
-    L.head = take(16);
-    for (int k = 0; k < 2; ++k) L.key[k] = take(8 * m);
-    for (int k = 0; k < 2; ++k) L.idx[k] = take(4 * m);
-    L.counts = take(uint64_t(kDigits) * L.pitch * 4);
-    L.totals = take(kDigits * 4);
-    L.flags = take(4 * m);
-    L.gh = take(4 * m);
-    L.gstate = take(4 * m);
-    L.garr = take(4 * m);
-    L.gend = take(4 * m);
-    L.gcnt = take(4 * m);
-    L.segt = take(12 * uint64_t(L.scan_tiles));
-    L.state0 = take(m);
-    L.gha = take(4 * m);
-    L.ccnt = take(4 * m);
-    L.clen = take(4 * m);
-    L.dnum = take(4 * m);
-    L.t1 = take(16 * uint64_t(L.scan_tiles));
-    L.t2 = take(8 * uint64_t(L.scan_tiles));
-    L.bytes = at;
+    L.head = c.take(16, 16);
+    for (int k = 0; k < 2; ++k) L.key[k] = c.take(8 * m, 16);
+    for (int k = 0; k < 2; ++k) L.idx[k] = c.take(4 * m, 16);
+    L.counts = c.take(uint64_t(kDigits) * L.pitch * 4, 16);
+    L.totals = c.take(kDigits * 4, 16);
+    L.flags = c.take(4 * m, 16);
+    L.gh = c.take(4 * m, 16);
+    L.gstate = c.take(4 * m, 16);
+    L.garr = c.take(4 * m, 16);
+    L.gend = c.take(4 * m, 16);
+    L.gcnt = c.take(4 * m, 16);
+    L.segt = c.take(12 * uint64_t(L.scan_tiles), 16);
+    L.state0 = c.take(m, 16);
+    L.gha = c.take(4 * m, 16);
+    L.ccnt = c.take(4 * m, 16);
+    L.clen = c.take(4 * m, 16);
+    L.dnum = c.take(4 * m, 16);
+    L.t1 = c.take(16 * uint64_t(L.scan_tiles), 16);
+    L.t2 = c.take(8 * uint64_t(L.scan_tiles), 16);
+    L.bytes = c.end();
     return L;
 }
 
@@ -741,53 +737,44 @@ int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = stream_ok(st, -1);
     if (rc != SCCSUM_OK) return rc;
+    Chain c{st};
     if (m == 0) {
-        return static_cast<int>(
-            launch_kernel(empty_kernel, dim3(1), dim3(kWave), 0, st, out->d_total, out->d_dgram_first));
+        c.launch(empty_kernel, dim3(1), dim3(kWave), 0, out->d_total, out->d_dgram_first);
+        return c.rc();
     }
 
     const Layout L = layout(m);
-    uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
-    auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(ws + at); };
-    auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(ws + at); };
+    const Workspace ws(d_workspace);
     const uint32_t n = static_cast<uint32_t>(m);
     const dim3 flat(static_cast<unsigned>(tiles_of(m, kFlatBlock))), sort(L.sort_tiles), scan(L.scan_tiles);
-    hipError_t e;
-#define REASM_LAUNCH(...)                      \
-    do {                                       \
-        e = launch_kernel(__VA_ARGS__);        \
-        if (e != hipSuccess) return static_cast<int>(e); \
-    } while (0)
+    const dim3 flat_block(kFlatBlock), sort_block(kSortBlock), scan_block(kScanBlock);
 
-    REASM_LAUNCH(key_kernel, flat, dim3(kFlatBlock), 0, st, d_rec, n, u64(L.key[0]), u32(L.idx[0]));
+    c.launch(key_kernel, flat, flat_block, 0, d_rec, n, ws.u64(L.key[0]), ws.u32(L.idx[0]));
     for (int p = 0; p < kPasses; ++p) {  // an even number of passes: the sorted order ends in key[0] / idx[0]
-        const uint64_t* const kin = u64(L.key[p & 1]);
-        const uint32_t* const iin = u32(L.idx[p & 1]);
-        REASM_LAUNCH(sort_count_kernel, sort, dim3(kSortBlock), 0, st, kin, n, kPassShift[p], kPassMask[p],
-                     u32(L.counts), L.pitch);
-        REASM_LAUNCH(scan_rows_kernel<>, dim3(kDigits), dim3(kWave), 0, st, u32(L.counts), L.sort_tiles, L.pitch,
-                     u32(L.totals));
-        REASM_LAUNCH(sort_scatter_kernel, sort, dim3(kSortBlock), 0, st, kin, iin, n, kPassShift[p], kPassMask[p],
-                     static_cast<const uint32_t*>(u32(L.counts)), L.pitch, static_cast<const uint32_t*>(u32(L.totals)),
-                     u64(L.key[(p + 1) & 1]), u32(L.idx[(p + 1) & 1]));
+        const uint64_t* const kin = ws.u64(L.key[p & 1]);
+        const uint32_t* const iin = ws.u32(L.idx[p & 1]);
+        c.launch(sort_count_kernel, sort, sort_block, 0, kin, n, kPassShift[p], kPassMask[p], ws.u32(L.counts),
+                 L.pitch);
+        c.launch(scan_rows_kernel<>, dim3(kDigits), dim3(kWave), 0, ws.u32(L.counts), L.sort_tiles, L.pitch,
+                 ws.u32(L.totals));
+        c.launch(sort_scatter_kernel, sort, sort_block, 0, kin, iin, n, kPassShift[p], kPassMask[p], ws.u32(L.counts),
+                 L.pitch, ws.u32(L.totals), ws.u64(L.key[(p + 1) & 1]), ws.u32(L.idx[(p + 1) & 1]));
     }
     static_assert(kPasses % 2 == 0, "the sorted order must end where it started");
-    const uint64_t* const skey = u64(L.key[0]);
-    const uint32_t* const sidx = u32(L.idx[0]);
-    const Groups G{u32(L.gstate), u32(L.garr), u32(L.gend), u32(L.gcnt)};
-    REASM_LAUNCH(detect_kernel, flat, dim3(kFlatBlock), 0, st, d_rec, skey, sidx, n, u32(L.flags));
-    REASM_LAUNCH(seg_tile_kernel, scan, dim3(kScanBlock), 0, st, static_cast<const uint32_t*>(u32(L.flags)), sidx, n,
-                 u32(L.segt));
-    REASM_LAUNCH(seg_carry_kernel, dim3(1), dim3(kScanBlock), 0, st, u32(L.segt), L.scan_tiles);
-    REASM_LAUNCH(seg_place_kernel, scan, dim3(kScanBlock), 0, st, d_rec, static_cast<const uint32_t*>(u32(L.flags)),
-                 sidx, n, static_cast<const uint32_t*>(u32(L.segt)), u32(L.gh), G);
-    REASM_LAUNCH(classify_kernel, flat, dim3(kFlatBlock), 0, st, sidx, static_cast<const uint32_t*>(u32(L.gh)), G, n,
-                 ws + L.state0, u32(L.gha), u32(L.ccnt), u32(L.clen));
-    const uint32_t* const ccnt = u32(L.ccnt);
-    const uint32_t* const clen = u32(L.clen);
-    REASM_LAUNCH(dg_tile_kernel, scan, dim3(kScanBlock), 0, st, ccnt, clen, n, u64(L.t1));
-    REASM_LAUNCH(dg_carry_kernel, dim3(1), dim3(kScanBlock), 0, st, ccnt, clen, n, u64(L.t1), L.scan_tiles,
-                 max_out_bytes, u64(L.head), out->d_total, out->d_dgram_first);
+    const uint64_t* const skey = ws.u64(L.key[0]);
+    const uint32_t* const sidx = ws.u32(L.idx[0]);
+    const Groups G{ws.u32(L.gstate), ws.u32(L.garr), ws.u32(L.gend), ws.u32(L.gcnt)};
+    c.launch(detect_kernel, flat, flat_block, 0, d_rec, skey, sidx, n, ws.u32(L.flags));
+    c.launch(seg_tile_kernel, scan, scan_block, 0, ws.u32(L.flags), sidx, n, ws.u32(L.segt));
+    c.launch(seg_carry_kernel, dim3(1), scan_block, 0, ws.u32(L.segt), L.scan_tiles);
+    c.launch(seg_place_kernel, scan, scan_block, 0, d_rec, ws.u32(L.flags), sidx, n, ws.u32(L.segt), ws.u32(L.gh), G);
+    c.launch(classify_kernel, flat, flat_block, 0, sidx, ws.u32(L.gh), G, n, ws.at<uint8_t>(L.state0), ws.u32(L.gha),
+             ws.u32(L.ccnt), ws.u32(L.clen));
+    const uint32_t* const ccnt = ws.u32(L.ccnt);
+    const uint32_t* const clen = ws.u32(L.clen);
+    c.launch(dg_tile_kernel, scan, scan_block, 0, ccnt, clen, n, ws.u64(L.t1));
+    c.launch(dg_carry_kernel, dim3(1), scan_block, 0, ccnt, clen, n, ws.u64(L.t1), L.scan_tiles, max_out_bytes,
+             ws.u64(L.head), out->d_total, out->d_dgram_first);
     Rss R{};
     R.hash = out->d_dgram_hash;
     if (key) {
@@ -803,19 +790,16 @@ int sccsum_ipv4_reasm(const sccsum_frag_rec* d_rec, uint64_t m, uint64_t max_out
     }
     const Dgrams D{out->d_dgram_first, out->d_dgram_off, out->d_dgram_len,
                    out->d_dgram_seed,  out->d_dgram_head, out->d_dgram_last};
-    REASM_LAUNCH(dg_place_kernel, scan, dim3(kScanBlock), 0, st, d_rec, sidx, ccnt, clen,
-                 static_cast<const uint32_t*>(u32(L.gha)), n, static_cast<const uint64_t*>(u64(L.t1)),
-                 static_cast<const uint64_t*>(u64(L.head)), u32(L.dnum), D, R);
-    REASM_LAUNCH(emit_kernel, flat, dim3(kFlatBlock), 0, st, d_rec, sidx, static_cast<const uint32_t*>(u32(L.gh)), G,
-                 static_cast<const uint32_t*>(u32(L.dnum)), n, static_cast<const uint32_t*>(out->d_dgram_first),
-                 static_cast<const uint64_t*>(out->d_dgram_off), out->d_desc);
-    const Final F{ws + L.state0, u32(L.gha), u32(L.garr), u32(L.dnum), n};
-    REASM_LAUNCH(st_tile_kernel, scan, dim3(kScanBlock), 0, st, F, u64(L.t2));
-    REASM_LAUNCH(st_carry_kernel, dim3(1), dim3(kScanBlock), 0, st, u64(L.t2), L.scan_tiles, out->d_total);
-    REASM_LAUNCH(st_place_kernel, scan, dim3(kScanBlock), 0, st, d_rec, F, static_cast<const uint64_t*>(u64(L.t2)),
-                 out->d_pending, out->d_host, out->d_rec_state);
-#undef REASM_LAUNCH
-    return SCCSUM_OK;
+    c.launch(dg_place_kernel, scan, scan_block, 0, d_rec, sidx, ccnt, clen, ws.u32(L.gha), n, ws.u64(L.t1),
+             ws.u64(L.head), ws.u32(L.dnum), D, R);
+    c.launch(emit_kernel, flat, flat_block, 0, d_rec, sidx, ws.u32(L.gh), G, ws.u32(L.dnum), n, out->d_dgram_first,
+             out->d_dgram_off, out->d_desc);
+    const Final F{ws.at<uint8_t>(L.state0), ws.u32(L.gha), ws.u32(L.garr), ws.u32(L.dnum), n};
+    c.launch(st_tile_kernel, scan, scan_block, 0, F, ws.u64(L.t2));
+    c.launch(st_carry_kernel, dim3(1), scan_block, 0, ws.u64(L.t2), L.scan_tiles, out->d_total);
+    c.launch(st_place_kernel, scan, scan_block, 0, d_rec, F, ws.u64(L.t2), out->d_pending, out->d_host,
+             out->d_rec_state);
+    return c.rc();
 }
 
 }  // extern "C"

@@ -46,8 +46,9 @@
 
 namespace send {
 
-using host_launch::launch_kernel;
+using host_launch::Chain;
 using host_launch::misaligned;
+using host_launch::stream_ok;
 using wire::tiles_of;
 
 constexpr int kWave = 64;
@@ -387,32 +388,25 @@ int sccsum_ipv4_send(const sccsum_send_opts* opts, void* d_l4, uint64_t l4_bytes
     }
     // the launches run on the stream's device, which must be the data's: the current one
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = -1, sd = -1;  // dev stays -1 when there is no current device to ask for
-    hipError_t e = host_launch::stream_devices(st, &dev, &sd);
-    if (e != hipSuccess) return e == hipErrorNoDevice && dev < 0 ? SCCSUM_ENODEV : static_cast<int>(e);
-    if (sd != dev) return SCCSUM_EINVAL;
+    const int rc = stream_ok(st, -1);
+    if (rc != SCCSUM_OK) return rc;
 
     const Batch B{d_off, d_len, d_proto, l4_bytes_len, n, opts->mtu, opts->flags};
     const uint64_t ntiles = tiles_of(n, kSendTile);
     uint64_t* const ws = static_cast<uint64_t*>(d_workspace);
-    if (ntiles) {
-        e = launch_kernel(send_count_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), 0, st, B, ws);
-        if (e != hipSuccess) return static_cast<int>(e);
-    }
-    e = launch_kernel(send_scan_kernel, dim3(1), dim3(kTileBlock), 0, st, B, ws, ntiles, max_frames, max_out_bytes,
-                      d_first, d_dgram_first, d_total);
-    if (e != hipSuccess) return static_cast<int>(e);
-    if (!ntiles) return SCCSUM_OK;
-    e = launch_kernel(send_place_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kTileBlock), 0, st, B, ws, ntiles,
-                      static_cast<uint8_t*>(d_l4), d_l4sum, d_dgram_first, d_status);
-    if (e != hipSuccess) return static_cast<int>(e);
-    if (max_frames == 0) return SCCSUM_OK;
+    const dim3 tiles(static_cast<unsigned>(ntiles)), block(kTileBlock);
+    Chain c{st};
+    if (ntiles) c.launch(send_count_kernel, tiles, block, 0, B, ws);
+    c.launch(send_scan_kernel, dim3(1), block, 0, B, ws, ntiles, max_frames, max_out_bytes, d_first, d_dgram_first,
+             d_total);
+    if (!ntiles) return c.rc();
+    c.launch(send_place_kernel, tiles, block, 0, B, ws, ntiles, d_l4, d_l4sum, d_dgram_first, d_status);
+    if (max_frames == 0) return c.rc();
     const uint64_t blocks = std::min<uint64_t>((max_frames + kEmitTile - 1) / kEmitTile, kEmitMaxBlocks);
     const Out O{d_hdr, d_desc, d_first, d_out_off, d_out_len};
-    e = launch_kernel(send_emit_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kEmitBlock), 0, st, B,
-                      static_cast<const uint64_t*>(ws), ntiles, static_cast<const uint8_t*>(d_l4), d_dst, d_id,
-                      static_cast<const uint32_t*>(d_dgram_first), opts->src_host, O);
-    return static_cast<int>(e);
+    c.launch(send_emit_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kEmitBlock), 0, B, ws, ntiles, d_l4, d_dst, d_id,
+             d_dgram_first, opts->src_host, O);
+    return c.rc();
 }
 
 }  // extern "C"

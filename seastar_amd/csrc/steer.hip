@@ -42,9 +42,10 @@
 namespace steer {
 
 using bucket_pass::pitch_of;
-using host_launch::launch_kernel;
+using host_launch::Chain;
+using host_launch::device_ok;
 using host_launch::misaligned;
-using wire::kMaxDevices;
+using host_launch::upload;
 using wire::status_passes;
 
 constexpr int kBlock = 256;              // threads per block of the count / scatter kernels
@@ -263,10 +264,8 @@ int sccsum_steer_create(int device, const sccsum_steer_map* map, sccsum_steer** 
             if (map->sw_reta[q * kRetaSize + i] >= map->ncpu) return SCCSUM_EINVAL;
         }
     }
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess) return e == hipErrorNoDevice ? SCCSUM_ENODEV : static_cast<int>(e);
-    if (device < 0 || device >= ndev || device >= kMaxDevices) return SCCSUM_ENODEV;
+    int rc = device_ok(device);
+    if (rc != SCCSUM_OK) return rc;
     auto* s = new (std::nothrow) sccsum_steer;
     if (!s) return static_cast<int>(hipErrorOutOfMemory);
     s->device = device;
@@ -288,30 +287,20 @@ int sccsum_steer_create(int device, const sccsum_steer_map* map, sccsum_steer** 
     s->map.redir = nullptr;
     s->map.sw_reta = nullptr;
     s->map.sw_reta_set = nullptr;
-    int cur = 0;
-    e = hipGetDevice(&cur);
-    if (e == hipSuccess) e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        void* d = nullptr;
-        e = hipMalloc(&d, blob.size());
-        if (e == hipSuccess) {
-            s->d_tables = static_cast<uint8_t*>(d);
-            e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
-        }
-        (void)hipSetDevice(cur);  // the caller's binding is put back
-    }
-    if (e != hipSuccess) {
-        if (s->d_tables) (void)hipFree(s->d_tables);
+    void* d[1];
+    rc = upload(device, {{blob.data(), blob.size()}}, d);
+    if (rc != SCCSUM_OK) {
         delete s;
-        return static_cast<int>(e);
+        return rc;
     }
+    s->d_tables = static_cast<uint8_t*>(d[0]);
     *out = s;
     return SCCSUM_OK;
 }
 
 int sccsum_steer_destroy(sccsum_steer* s) {
     if (!s) return SCCSUM_OK;
-    const hipError_t e = s->d_tables ? hipFree(s->d_tables) : hipSuccess;
+    const hipError_t e = host_launch::free_all({s->d_tables});
     delete s;
     return static_cast<int>(e);
 }
@@ -362,7 +351,7 @@ int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const ui
     // the launches run on the stream's device, where the tables must lie
     const hipStream_t st = static_cast<hipStream_t>(stream);
     int cur = 0, dev = 0;
-    hipError_t e = host_launch::stream_devices(st, &cur, &dev);
+    const hipError_t e = host_launch::stream_devices(st, &cur, &dev);
     if (e != hipSuccess) return static_cast<int>(e);
     if (dev != s->device) return SCCSUM_EINVAL;
 
@@ -371,20 +360,17 @@ int sccsum_steer_run(const sccsum_steer* s, int mode, uint32_t src_cpu, const ui
     const uint32_t buckets = P.ncpu + 1;
     uint32_t* const ws = static_cast<uint32_t*>(d_workspace);
     const size_t lds = size_t(P.rows) * kRetaSize + (P.rows > 1 ? ((P.redir_size + 15u) & ~15u) : 0u);
-    if (ntiles) {
-        e = launch_kernel(steer_count_kernel, dim3(ntiles), dim3(kBlock), lds, st, d_hash, d_status, n, d_cpu, ws, pitch,
-                          P);
-        if (e != hipSuccess) return static_cast<int>(e);
+    Chain c{st};
+    if (ntiles) c.launch(steer_count_kernel, dim3(ntiles), dim3(kBlock), lds, d_hash, d_status, n, d_cpu, ws, pitch, P);
+    if (c.ok()) {
+        c.e = bucket_pass::scan_buckets<kScanBlock, kMaxBuckets>(st, ws, ntiles, pitch, buckets, d_first,
+                                                                 ws + uint64_t(buckets) * pitch);
     }
-    e = bucket_pass::scan_buckets<kScanBlock, kMaxBuckets>(st, ws, ntiles, pitch, buckets, d_first,
-                                                           ws + uint64_t(buckets) * pitch);
-    if (e != hipSuccess) return static_cast<int>(e);
     if (ntiles && d_order) {
-        e = launch_kernel(steer_scatter_kernel, dim3(ntiles), dim3(kBlock), lds, st, d_hash, d_status, n,
-                          static_cast<const uint32_t*>(ws), pitch, static_cast<const uint32_t*>(d_first), d_order, P);
-        if (e != hipSuccess) return static_cast<int>(e);
+        c.launch(steer_scatter_kernel, dim3(ntiles), dim3(kBlock), lds, d_hash, d_status, n, ws, pitch, d_first, d_order,
+                 P);
     }
-    return SCCSUM_OK;
+    return c.rc();
 }
 
 }  // extern "C"

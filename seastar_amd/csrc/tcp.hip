@@ -53,13 +53,15 @@ namespace tcp {
 
 using bucket_pass::kDigits;
 using bucket_pass::scan_rows_kernel;
-using host_launch::launch_kernel;
+using host_launch::Chain;
+using host_launch::device_ok;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::upload;
+using host_launch::Workspace;
 using wave_scan::block_inclusive_scan;
 using wire::be16_at;
 using wire::be32_at;
-using wire::kMaxDevices;
 using wire::pseudo_seed;
 using wire::tiles_of;
 
@@ -525,23 +527,15 @@ Layout layout_of(uint64_t n) {
     Layout L{};
     L.ntiles = static_cast<uint32_t>(tiles_of(n, kTile));
     L.pitch = bucket_pass::pitch_of(L.ntiles);
-    uint64_t at = 0;
-    L.rec = at;
-    at += 32 * n;
-    L.addr = at;
-    at += 8 * n;
-    L.kv0 = at;
-    at += 8 * n;
-    L.kv1 = at;
-    at += 8 * n;
-    at = (at + 15u) & ~uint64_t(15);
-    L.counts = at;
-    at += uint64_t(kDigits) * L.pitch * 4u;
-    L.totals = at;
-    at += kDigits * 4u;
-    L.tcount = at;
-    at += (uint64_t(L.ntiles) + 4u) * 4u;
-    L.bytes = (at + 15u) & ~uint64_t(15);
+    host_launch::Carver c;
+    L.rec = c.take(32 * n);
+    L.addr = c.take(8 * n);
+    L.kv0 = c.take(8 * n);
+    L.kv1 = c.take(8 * n);
+    L.counts = c.take(uint64_t(kDigits) * L.pitch * 4u, 16);
+    L.totals = c.take(kDigits * 4u);
+    L.tcount = c.take((uint64_t(L.ntiles) + 4u) * 4u);
+    L.bytes = c.end();
     return L;
 }
 
@@ -562,38 +556,19 @@ int sccsum_tcp_conns_create(int device, const sccsum_tcp_conn* conns, uint32_t n
     if (!out) return SCCSUM_EINVAL;
     *out = nullptr;
     sccsum_tcp_conns* t = nullptr;
-    const int rc = new_conns(conns, nconns, listen, nlisten, &t);
+    int rc = new_conns(conns, nconns, listen, nlisten, &t);   // duplicates show only while the table is built
     if (rc != SCCSUM_OK) return rc;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || device < 0 || device >= ndev || device >= kMaxDevices) {
+    void* d[2];
+    rc = device_ok(device);
+    if (rc == SCCSUM_OK) {
+        rc = upload(device, {{t->slots.data(), t->slots.size() * sizeof(uint4)}, {t->listening.data(), kPorts}}, d);
+    }
+    if (rc != SCCSUM_OK) {
         delete t;
-        return e == hipSuccess || e == hipErrorNoDevice ? SCCSUM_ENODEV : static_cast<int>(e);
+        return rc;
     }
-    int cur = 0;
-    e = hipGetDevice(&cur);
-    if (e == hipSuccess) e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        void* d = nullptr;
-        const size_t bytes = t->slots.size() * sizeof(uint4);
-        e = hipMalloc(&d, bytes);
-        if (e == hipSuccess) {
-            t->d_slots = static_cast<uint4*>(d);
-            e = hipMemcpy(d, t->slots.data(), bytes, hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMalloc(&d, kPorts);
-        if (e == hipSuccess) {
-            t->d_listening = static_cast<uint8_t*>(d);
-            e = hipMemcpy(d, t->listening.data(), kPorts, hipMemcpyHostToDevice);
-        }
-        (void)hipSetDevice(cur);  // the caller's binding is put back
-    }
-    if (e != hipSuccess) {
-        if (t->d_slots) (void)hipFree(t->d_slots);
-        if (t->d_listening) (void)hipFree(t->d_listening);
-        delete t;
-        return static_cast<int>(e);
-    }
+    t->d_slots = static_cast<uint4*>(d[0]);
+    t->d_listening = static_cast<uint8_t*>(d[1]);
     t->device = device;
     *out = t;
     return SCCSUM_OK;
@@ -601,9 +576,7 @@ int sccsum_tcp_conns_create(int device, const sccsum_tcp_conn* conns, uint32_t n
 
 int sccsum_tcp_conns_destroy(sccsum_tcp_conns* t) {
     if (!t) return SCCSUM_OK;
-    hipError_t e = t->d_slots ? hipFree(t->d_slots) : hipSuccess;
-    const hipError_t e2 = t->d_listening ? hipFree(t->d_listening) : hipSuccess;
-    if (e == hipSuccess) e = e2;
+    const hipError_t e = host_launch::free_all({t->d_slots, t->d_listening});
     delete t;
     return static_cast<int>(e);
 }
@@ -661,54 +634,41 @@ int sccsum_tcp_rx(const void* d_bytes, uint64_t bytes_len, const uint64_t* d_off
     if (rc != SCCSUM_OK) return rc;
 
     const Layout L = layout_of(n);
-    uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
-    uint4* const rec = reinterpret_cast<uint4*>(ws + L.rec);
-    uint2* const addr = reinterpret_cast<uint2*>(ws + L.addr);
-    uint2* kv = reinterpret_cast<uint2*>(ws + L.kv0);
-    uint2* kv_other = reinterpret_cast<uint2*>(ws + L.kv1);
-    uint32_t* const counts = reinterpret_cast<uint32_t*>(ws + L.counts);
-    uint32_t* const totals = reinterpret_cast<uint32_t*>(ws + L.totals);
-    uint32_t* const tcount = reinterpret_cast<uint32_t*>(ws + L.tcount);
+    const Workspace ws(d_workspace);
+    uint4* const rec = ws.at<uint4>(L.rec);
+    uint2* const addr = ws.at<uint2>(L.addr);
+    uint2* kv = ws.at<uint2>(L.kv0);
+    uint2* kv_other = ws.at<uint2>(L.kv1);
+    uint32_t* const counts = ws.u32(L.counts);
+    uint32_t* const totals = ws.u32(L.totals);
+    uint32_t* const tcount = ws.u32(L.tcount);
     const RxOut O{d_first, d_order, reinterpret_cast<uint2*>(d_seg), d_src, d_run_conn, d_run_first,
                   static_cast<uint32_t*>(d_rst), d_rst_dst, d_total};
     const uint32_t nconns = conns->nconns;
     const dim3 tiles(L.ntiles), block(kBlock);
-    hipError_t e = hipSuccess;
+    Chain c{st};
     if (L.ntiles) {
         const Decode D{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, d_len, nbatch, d_status, d_index, n,
                        need, reject, host_address, conns->d_slots, (1u << conns->bits) - 1u, nconns,
                        conns->d_listening};
-        e = launch_kernel(decode_kernel, tiles, block, 0, st, D, d_class, rec, addr, kv, counts, L.pitch);
+        c.launch(decode_kernel, tiles, block, 0, D, d_class, rec, addr, kv, counts, L.pitch);
         const int passes = passes_of(nconns);
-        for (int p = 0; p < passes && e == hipSuccess; ++p) {
-            if (p != 0) {
-                e = launch_kernel(sort_count_kernel, tiles, block, 0, st, static_cast<const uint2*>(kv), n, 8 * p, counts,
-                                  L.pitch);
-                if (e != hipSuccess) break;
-            }
-            e = launch_kernel(scan_rows_kernel<>, dim3(kDigits), dim3(kWave), 0, st, counts, L.ntiles, L.pitch, totals);
-            if (e != hipSuccess) break;
-            e = launch_kernel(sort_scatter_kernel, tiles, block, 0, st, static_cast<const uint2*>(kv), n, 8 * p,
-                              static_cast<const uint32_t*>(counts), L.pitch, static_cast<const uint32_t*>(totals),
-                              kv_other);
+        for (int p = 0; p < passes; ++p) {
+            if (p != 0) c.launch(sort_count_kernel, tiles, block, 0, kv, n, 8 * p, counts, L.pitch);
+            c.launch(scan_rows_kernel<>, dim3(kDigits), dim3(kWave), 0, counts, L.ntiles, L.pitch, totals);
+            c.launch(sort_scatter_kernel, tiles, block, 0, kv, n, 8 * p, counts, L.pitch, totals, kv_other);
             uint2* const t = kv;
             kv = kv_other;
             kv_other = t;
         }
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = launch_kernel(gather_kernel, tiles, block, 0, st, static_cast<const uint2*>(kv), n, nconns,
-                          static_cast<const uint4*>(rec), static_cast<const uint2*>(addr), O, tcount);
-        if (e != hipSuccess) return static_cast<int>(e);
+        c.launch(gather_kernel, tiles, block, 0, kv, n, nconns, rec, addr, O, tcount);
     }
-    e = launch_kernel(run_carry_kernel, dim3(1), block, 0, st, tcount, L.ntiles, O);
-    if (e != hipSuccess || !L.ntiles) return static_cast<int>(e);
-    e = launch_kernel(run_place_kernel, tiles, block, 0, st, static_cast<const uint2*>(kv), n, nconns,
-                      static_cast<const uint32_t*>(tcount), O);
-    if (e != hipSuccess) return static_cast<int>(e);
+    c.launch(run_carry_kernel, dim3(1), block, 0, tcount, L.ntiles, O);
+    if (!L.ntiles) return c.rc();
+    c.launch(run_place_kernel, tiles, block, 0, kv, n, nconns, tcount, O);
     const uint64_t blocks = (n + kFlatBlock - 1) / kFlatBlock;
-    e = launch_kernel(reset_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kFlatBlock), 0, st,
-                      static_cast<const uint2*>(kv), static_cast<const uint2*>(addr), flags, O);
-    return static_cast<int>(e);
+    c.launch(reset_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kFlatBlock), 0, kv, addr, flags, O);
+    return c.rc();
 }
 
 int sccsum_tcp_send(const sccsum_tcp_opts* opts, void* d_bytes, uint64_t bytes_len, const uint64_t* d_off,
@@ -736,7 +696,9 @@ int sccsum_tcp_send(const sccsum_tcp_opts* opts, void* d_bytes, uint64_t bytes_l
                  opts->src_host, opts->flags};
     const SendOut O{d_l4_off, d_l4_len, d_sum_len, d_seed, d_tso_seg, d_proto, d_needs_csum, d_status};
     const uint64_t blocks = (n + kFlatBlock - 1) / kFlatBlock;
-    return static_cast<int>(launch_kernel(send_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kFlatBlock), 0, st, S, O));
+    Chain c{st};
+    c.launch(send_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kFlatBlock), 0, S, O);
+    return c.rc();
 }
 
 }  // extern "C"

@@ -45,9 +45,10 @@
 namespace tcp_ack {
 
 using array_scan::scan_array;
-using host_launch::launch_kernel;
+using host_launch::Chain;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::Workspace;
 using wave_scan::block_inclusive_scan;
 using wire::tiles_of;
 
@@ -313,20 +314,16 @@ Layout layout_of(uint64_t n, uint64_t nconns, uint64_t nq) {
     Layout L{};
     const uint64_t qtiles = tiles_of(nq, array_scan::kTile) + 1;
     const uint64_t rblocks = tiles_of(n < nconns ? n : nconns, kBlock) + 1;
-    uint64_t at = 0;
-    const auto take = [&](uint64_t* w, uint64_t bytes) {
-        *w = at;
-        at += bytes;
-    };
-    take(&L.G, 8 * (nq + 1));
-    take(&L.gt, 8 * qtiles);
-    take(&L.pair, 8 * n);
-    take(&L.t_taken, 8 * rblocks);
-    take(&L.t_popped, 8 * rblocks);
-    take(&L.t_acked, 8 * rblocks);
-    take(&L.Z, 4 * (nq + 1));
-    take(&L.zt, 4 * qtiles);
-    L.bytes = (at + 15u) & ~uint64_t(15);
+    host_launch::Carver c;
+    L.G = c.take(8 * (nq + 1));
+    L.gt = c.take(8 * qtiles);
+    L.pair = c.take(8 * n);
+    L.t_taken = c.take(8 * rblocks);
+    L.t_popped = c.take(8 * rblocks);
+    L.t_acked = c.take(8 * rblocks);
+    L.Z = c.take(4 * (nq + 1));
+    L.zt = c.take(4 * qtiles);
+    L.bytes = c.end();
     return L;
 }
 
@@ -362,30 +359,24 @@ int sccsum_tcp_rx_acks(const sccsum_tcp_seg* d_seg, const uint32_t* d_first, con
     if (rc != SCCSUM_OK) return rc;
 
     const Layout L = layout_of(n, nconns, nq);
-    uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
-    const auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(ws + at); };
-    const auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(ws + at); };
+    const Workspace ws(d_workspace);
     const uint64_t max_runs = n < nconns ? n : nconns;
     const uint64_t rblocks = tiles_of(max_runs, kBlock);
     const uint32_t entries = static_cast<uint32_t>(nconns ? nq : 0);   // without a connection no entry is read
-    const In I{reinterpret_cast<const uint2*>(d_seg), d_first, reinterpret_cast<const uint4*>(d_ack), d_q_first, u64(L.G),
-               u32(L.Z), n, nconns, entries};
-    const Out O{reinterpret_cast<uint4*>(d_run), d_total, d_run_conn, d_run_first, d_rx_total, d_q_len, d_q_meta, d_q_tx,
-                now_ns, max_runs, u64(L.t_taken), u64(L.t_popped), u64(L.t_acked)};
-    uint2* const pair = reinterpret_cast<uint2*>(ws + L.pair);
-    hipError_t e = hipSuccess;
+    const In I{reinterpret_cast<const uint2*>(d_seg), d_first, reinterpret_cast<const uint4*>(d_ack), d_q_first,
+               ws.u64(L.G), ws.u32(L.Z), n, nconns, entries};
+    const Out O{reinterpret_cast<uint4*>(d_run), d_total, d_run_conn, d_run_first, d_rx_total, d_q_len, d_q_meta,
+                d_q_tx, now_ns, max_runs, ws.u64(L.t_taken), ws.u64(L.t_popped), ws.u64(L.t_acked)};
+    uint2* const pair = ws.at<uint2>(L.pair);
+    Chain c{st};
     if (rblocks != 0) {
-        e = scan_array<uint64_t>(st, array_scan::LoadLen{d_q_len}, entries, u64(L.gt), u64(L.G));
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = scan_array<uint32_t>(st, LoadZero{d_q_len}, entries, u32(L.zt), u32(L.Z));
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = launch_kernel(eval, dim3(static_cast<unsigned>(tiles_of(n, kBlock))), dim3(kBlock), 0, st, I, pair);
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = launch_kernel(walk, dim3(static_cast<unsigned>(rblocks)), dim3(kBlock), 0, st, I,
-                          static_cast<const uint2*>(pair), O);
-        if (e != hipSuccess) return static_cast<int>(e);
+        c.e = scan_array<uint64_t>(st, array_scan::LoadLen{d_q_len}, entries, ws.u64(L.gt), ws.u64(L.G));
+        if (c.ok()) c.e = scan_array<uint32_t>(st, LoadZero{d_q_len}, entries, ws.u32(L.zt), ws.u32(L.Z));
+        c.launch(eval, dim3(static_cast<unsigned>(tiles_of(n, kBlock))), dim3(kBlock), 0, I, pair);
+        c.launch(walk, dim3(static_cast<unsigned>(rblocks)), dim3(kBlock), 0, I, pair, O);
     }
-    return static_cast<int>(launch_kernel(totals, dim3(1), dim3(kBlock), 0, st, O, rblocks));
+    c.launch(totals, dim3(1), dim3(kBlock), 0, O, rblocks);
+    return c.rc();
 }
 
 }  // extern "C"

@@ -47,9 +47,10 @@
 
 namespace tcp_data {
 
-using host_launch::launch_kernel;
+using host_launch::Chain;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::Workspace;
 using wave_scan::block_inclusive_scan;
 using wire::tiles_of;
 
@@ -514,21 +515,14 @@ struct Layout {
 Layout layout_of(uint64_t n) {
     Layout L{};
     const uint64_t k = tiles_of(n, kTile) + 1;
-    uint64_t at = 0;
+    host_launch::Carver c;
     uint64_t* const wide[] = {&L.agg_sum, &L.in_sum, &L.hbytes, &L.rbytes, &L.bytes_in, &L.cnt_in};
-    for (uint64_t* w : wide) {
-        *w = at;
-        at += 8 * k;
-    }
+    for (uint64_t* w : wide) *w = c.take(8 * k);
     uint64_t* const narrow[] = {&L.agg_meta, &L.heads, &L.in_meta, &L.heads_before, &L.hcnt, &L.rcnt, &L.tflags,
                                 &L.stopped_in};
-    for (uint64_t* w : narrow) {
-        *w = at;
-        at += 4 * k;
-    }
-    L.cut = at;
-    at += 16;
-    L.bytes = (at + 15u) & ~uint64_t(15);
+    for (uint64_t* w : narrow) *w = c.take(4 * k);
+    L.cut = c.take(16);
+    L.bytes = c.end();
     return L;
 }
 
@@ -561,33 +555,28 @@ int sccsum_tcp_rx_data(const void* d_bytes, const sccsum_tcp_seg* d_seg, const u
     if (rc != SCCSUM_OK) return rc;
 
     const Layout L = layout_of(n);
-    uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
-    const auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(ws + at); };
-    const auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(ws + at); };
-    const Ws W{u64(L.agg_sum), u32(L.agg_meta), u32(L.heads), u64(L.in_sum), u32(L.in_meta), u32(L.heads_before),
-               u64(L.hbytes), u64(L.rbytes), u32(L.hcnt), u32(L.rcnt), u32(L.tflags), u64(L.bytes_in), u64(L.cnt_in),
-               u32(L.stopped_in), u32(L.cut)};
+    const Workspace ws(d_workspace);
+    const Ws W{ws.u64(L.agg_sum), ws.u32(L.agg_meta), ws.u32(L.heads), ws.u64(L.in_sum), ws.u32(L.in_meta),
+               ws.u32(L.heads_before), ws.u64(L.hbytes), ws.u64(L.rbytes), ws.u32(L.hcnt), ws.u32(L.rcnt),
+               ws.u32(L.tflags), ws.u64(L.bytes_in), ws.u64(L.cnt_in), ws.u32(L.stopped_in), ws.u32(L.cut)};
     const In I{reinterpret_cast<const uint2*>(d_seg), d_first, reinterpret_cast<const uint4*>(d_rcv), n, nconns};
-    const Out O{reinterpret_cast<uint2*>(d_run), reinterpret_cast<uint2*>(d_desc), d_total, d_run_first, d_rx_total,
-                reinterpret_cast<uint64_t>(d_bytes), max_bytes, n < nconns ? n : nconns};
-    const dim3 tiles(static_cast<unsigned>(tiles_of(n, kTile))), block(kBlock);
-    hipError_t e = hipSuccess;
-    if (n != 0) {
-        e = launch_kernel(sum_tile, tiles, block, 0, st, I, W);
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = launch_kernel(sum_carry, dim3(1), block, 0, st, I, W);
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = launch_kernel(stop_tile, tiles, block, 0, st, I, W);
-        if (e != hipSuccess) return static_cast<int>(e);
-    }
-    e = launch_kernel(stop_carry, dim3(1), block, 0, st, I, W, O);
-    if (e != hipSuccess || n == 0) return static_cast<int>(e);
-    e = launch_kernel(place, tiles, block, 0, st, I, W, O);
-    if (e != hipSuccess) return static_cast<int>(e);
     const uint64_t runs = n < nconns ? n : nconns;
-    if (runs == 0) return SCCSUM_OK;
+    const Out O{reinterpret_cast<uint2*>(d_run), reinterpret_cast<uint2*>(d_desc), d_total, d_run_first, d_rx_total,
+                reinterpret_cast<uint64_t>(d_bytes), max_bytes, runs};
+    const dim3 tiles(static_cast<unsigned>(tiles_of(n, kTile))), block(kBlock);
+    Chain c{st};
+    if (n != 0) {
+        c.launch(sum_tile, tiles, block, 0, I, W);
+        c.launch(sum_carry, dim3(1), block, 0, I, W);
+        c.launch(stop_tile, tiles, block, 0, I, W);
+    }
+    c.launch(stop_carry, dim3(1), block, 0, I, W, O);
+    if (n == 0) return c.rc();
+    c.launch(place, tiles, block, 0, I, W, O);
+    if (runs == 0) return c.rc();
     const uint64_t blocks = (runs + kFlatBlock - 1) / kFlatBlock;
-    return static_cast<int>(launch_kernel(cut_runs, dim3(static_cast<unsigned>(blocks)), dim3(kFlatBlock), 0, st, O));
+    c.launch(cut_runs, dim3(static_cast<unsigned>(blocks)), dim3(kFlatBlock), 0, O);
+    return c.rc();
 }
 
 }  // extern "C"

@@ -50,9 +50,10 @@ namespace tcp_listen {
 
 using bucket_pass::kDigits;
 using bucket_pass::scan_rows_kernel;
-using host_launch::launch_kernel;
+using host_launch::Chain;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::Workspace;
 using wave_scan::block_inclusive_scan;
 using wire::be32_at;
 using wire::tiles_of;
@@ -558,25 +559,21 @@ Layout layout_of(uint64_t m) {
     L.ntiles = static_cast<uint32_t>(tiles_of(m, kTile));
     L.pitch = bucket_pass::pitch_of(L.ntiles);
     L.bits = slot_bits(m);
-    uint64_t at = 0;
-    const auto take = [&](uint64_t* w, uint64_t bytes) {
-        *w = at;
-        at += (bytes + 15u) & ~uint64_t(15);
-    };
-    take(&L.key, 16 * m);
-    take(&L.kv0, 8 * m);
-    take(&L.kv1, 8 * m);
-    take(&L.counts, uint64_t(kDigits) * L.pitch * 4u);
-    take(&L.table, 4 * (uint64_t(1) << L.bits));
-    take(&L.port_start, 4 * uint64_t(kPorts));
-    take(&L.totals, 4 * uint64_t(kDigits));
-    take(&L.mark, 4 * m);
-    take(&L.new_pos, 4 * m);
-    take(&L.rst_pos, 4 * m);
-    take(&L.tc_new, 4 * (uint64_t(L.ntiles) + 4u));
-    take(&L.tc_rst, 4 * (uint64_t(L.ntiles) + 4u));
-    take(&L.sc, 4 * uint64_t(kScalars));
-    L.bytes = at;
+    host_launch::Carver c;
+    L.key = c.take(16 * m, 16);
+    L.kv0 = c.take(8 * m, 16);
+    L.kv1 = c.take(8 * m, 16);
+    L.counts = c.take(uint64_t(kDigits) * L.pitch * 4u, 16);
+    L.table = c.take(4 * (uint64_t(1) << L.bits), 16);
+    L.port_start = c.take(4 * uint64_t(kPorts), 16);
+    L.totals = c.take(4 * uint64_t(kDigits), 16);
+    L.mark = c.take(4 * m, 16);
+    L.new_pos = c.take(4 * m, 16);
+    L.rst_pos = c.take(4 * m, 16);
+    L.tc_new = c.take(4 * (uint64_t(L.ntiles) + 4u), 16);
+    L.tc_rst = c.take(4 * (uint64_t(L.ntiles) + 4u), 16);
+    L.sc = c.take(4 * uint64_t(kScalars), 16);
+    L.bytes = c.end();
     return L;
 }
 
@@ -616,21 +613,21 @@ int sccsum_tcp_listen(sccsum_tcp_listen_opts opts, const void* d_bytes, uint64_t
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = stream_ok(st, -1);
     if (rc != SCCSUM_OK) return rc;
+    Chain c{st};
     if (m_max == 0) {
-        return static_cast<int>(launch_kernel(totals_kernel, dim3(1), dim3(kWave), 0, st,
-                                              static_cast<const uint32_t*>(nullptr), d_total));
+        c.launch(totals_kernel, dim3(1), dim3(kWave), 0, nullptr, d_total);
+        return c.rc();
     }
 
     const Layout L = layout_of(m_max);
-    uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
-    const auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(ws + at); };
+    const Workspace ws(d_workspace);
     const uint32_t m = static_cast<uint32_t>(m_max);
     const In I{static_cast<const uint8_t*>(d_bytes), bytes_len, d_off, nbatch, d_first, d_order,
                reinterpret_cast<const uint2*>(d_seg), d_src, d_space, m};
-    const Ws W{reinterpret_cast<uint4*>(ws + L.key), reinterpret_cast<uint2*>(ws + L.kv0),
-               reinterpret_cast<uint2*>(ws + L.kv1), u32(L.table), static_cast<uint32_t>((uint64_t(1) << L.bits) - 1u),
-               u32(L.port_start), u32(L.counts), u32(L.totals), L.pitch, u32(L.mark), u32(L.new_pos), u32(L.rst_pos),
-               u32(L.tc_new), u32(L.tc_rst), u32(L.sc)};
+    const Ws W{ws.at<uint4>(L.key), ws.at<uint2>(L.kv0), ws.at<uint2>(L.kv1), ws.u32(L.table),
+               static_cast<uint32_t>((uint64_t(1) << L.bits) - 1u), ws.u32(L.port_start), ws.u32(L.counts),
+               ws.u32(L.totals), L.pitch, ws.u32(L.mark), ws.u32(L.new_pos), ws.u32(L.rst_pos), ws.u32(L.tc_new),
+               ws.u32(L.tc_rst), ws.u32(L.sc)};
     const Out O{d_class, reinterpret_cast<uint4*>(d_new), static_cast<uint32_t*>(d_synack), d_sa_off, d_sa_len,
                 reinterpret_cast<uint32_t*>(d_sa_out), static_cast<uint32_t*>(d_rst), d_rst_dst, d_total};
     const dim3 tiles(L.ntiles), block(kBlock), rows(kDigits), wave(kWave);
@@ -639,45 +636,34 @@ int sccsum_tcp_listen(sccsum_tcp_listen_opts opts, const void* d_bytes, uint64_t
     const dim3 flat(static_cast<unsigned>(tiles_of(m_max, kFlatBlock))), flat_block(kFlatBlock);
     const uint32_t* const n_all = W.sc + kM;
     const uint32_t* const n_cands = W.sc + kCands;
-    const uint32_t* const counts = W.counts;
-    const uint32_t* const totals = W.totals;
 
-    hipError_t e = launch_kernel(clear_kernel, clear_grid, block, 0, st, I, W);
-    if (e == hipSuccess) e = launch_kernel(key_kernel, tiles, block, 0, st, I, W);
-    if (e == hipSuccess) e = launch_kernel(insert_kernel, tiles, block, 0, st, W);
-    if (e == hipSuccess) e = launch_kernel(cand_kernel, tiles, block, 0, st, W);
+    c.launch(clear_kernel, clear_grid, block, 0, I, W);
+    c.launch(key_kernel, tiles, block, 0, I, W);
+    c.launch(insert_kernel, tiles, block, 0, W);
+    c.launch(cand_kernel, tiles, block, 0, W);
     // the candidates by port: two stable 8-bit passes, kv0 -> kv1 -> kv0
-    if (e == hipSuccess) e = launch_kernel(scan_rows_kernel<>, rows, wave, 0, st, W.counts, L.ntiles, L.pitch, W.totals);
-    if (e == hipSuccess) e = launch_kernel(sum_kernel, dim3(1), flat_block, 0, st, totals, W.sc);
-    if (e == hipSuccess) {
-        e = launch_kernel(sort_scatter_kernel, tiles, block, 0, st, static_cast<const uint2*>(W.kv0), n_all, 0, counts,
-                          L.pitch, totals, W.kv1, m);
+    c.launch(scan_rows_kernel<>, rows, wave, 0, W.counts, L.ntiles, L.pitch, W.totals);
+    c.launch(sum_kernel, dim3(1), flat_block, 0, W.totals, W.sc);
+    c.launch(sort_scatter_kernel, tiles, block, 0, W.kv0, n_all, 0, W.counts, L.pitch, W.totals, W.kv1, m);
+    c.launch(sort_count_kernel, tiles, block, 0, W.kv1, n_cands, 8, W.counts, L.pitch);
+    c.launch(scan_rows_kernel<>, rows, wave, 0, W.counts, L.ntiles, L.pitch, W.totals);
+    c.launch(sort_scatter_kernel, tiles, block, 0, W.kv1, n_cands, 8, W.counts, L.pitch, W.totals, W.kv0, m);
+    c.launch(head_kernel, tiles, block, 0, W);
+    c.launch(rank_kernel, tiles, block, 0, I, W);
+    c.launch(stop_kernel, tiles, block, 0, W);
+    c.launch(class_kernel, tiles, block, 0, I, W, d_class);
+    if (c.ok()) {
+        c.e = compact::run<kBlock>(st, OfClass{d_class, W.sc, SCCSUM_TCP_LISTEN_NEW}, L.ntiles, W.tc_new, W.sc + kNew,
+                                   W.new_pos);
     }
-    if (e == hipSuccess) {
-        e = launch_kernel(sort_count_kernel, tiles, block, 0, st, static_cast<const uint2*>(W.kv1), n_cands, 8, W.counts,
-                          L.pitch);
+    if (c.ok()) {
+        c.e = compact::run<kBlock>(st, OfClass{d_class, W.sc, SCCSUM_TCP_LISTEN_RESET}, L.ntiles, W.tc_rst,
+                                   W.sc + kResets, W.rst_pos);
     }
-    if (e == hipSuccess) e = launch_kernel(scan_rows_kernel<>, rows, wave, 0, st, W.counts, L.ntiles, L.pitch, W.totals);
-    if (e == hipSuccess) {
-        e = launch_kernel(sort_scatter_kernel, tiles, block, 0, st, static_cast<const uint2*>(W.kv1), n_cands, 8, counts,
-                          L.pitch, totals, W.kv0, m);
-    }
-    if (e == hipSuccess) e = launch_kernel(head_kernel, tiles, block, 0, st, W);
-    if (e == hipSuccess) e = launch_kernel(rank_kernel, tiles, block, 0, st, I, W);
-    if (e == hipSuccess) e = launch_kernel(stop_kernel, tiles, block, 0, st, W);
-    if (e == hipSuccess) e = launch_kernel(class_kernel, tiles, block, 0, st, I, W, d_class);
-    if (e == hipSuccess) {
-        e = compact::run<kBlock>(st, OfClass{d_class, W.sc, SCCSUM_TCP_LISTEN_NEW}, L.ntiles, W.tc_new, W.sc + kNew,
-                                 W.new_pos);
-    }
-    if (e == hipSuccess) {
-        e = compact::run<kBlock>(st, OfClass{d_class, W.sc, SCCSUM_TCP_LISTEN_RESET}, L.ntiles, W.tc_rst, W.sc + kResets,
-                                 W.rst_pos);
-    }
-    if (e == hipSuccess) e = launch_kernel(new_kernel, flat, flat_block, 0, st, I, W, O, opts);
-    if (e == hipSuccess) e = launch_kernel(reset_kernel, flat, flat_block, 0, st, I, W, O, opts.flags);
-    if (e == hipSuccess) e = launch_kernel(totals_kernel, dim3(1), wave, 0, st, static_cast<const uint32_t*>(W.sc), d_total);
-    return static_cast<int>(e);
+    c.launch(new_kernel, flat, flat_block, 0, I, W, O, opts);
+    c.launch(reset_kernel, flat, flat_block, 0, I, W, O, opts.flags);
+    c.launch(totals_kernel, dim3(1), wave, 0, W.sc, d_total);
+    return c.rc();
 }
 
 }  // extern "C"

@@ -46,9 +46,10 @@ namespace tcp_tx_data {
 
 using array_scan::LoadLen;
 using array_scan::scan_array;   // the exclusive scan of an array: tile / carry / place
-using host_launch::launch_kernel;
+using host_launch::Chain;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::Workspace;
 using wave_scan::block_inclusive_scan;
 using wire::tiles_of;
 
@@ -385,23 +386,19 @@ struct Layout {
 Layout layout_of(uint64_t nconns, uint64_t nbuf) {
     Layout L{};
     const uint64_t btiles = tiles_of(nbuf, kTile) + 1, ctiles = tiles_of(nconns, kTile) + 1;
-    uint64_t at = 0;
-    const auto take = [&](uint64_t* w, uint64_t bytes) {
-        *w = at;
-        at += bytes;
-    };
-    take(&L.G, 8 * (nbuf + 1));
-    take(&L.bt, 8 * btiles);
-    take(&L.c_segs, 8 * nconns);
-    take(&L.c_bytes, 8 * nconns);
-    take(&L.c_pieces, 8 * nconns);
-    take(&L.t_segs, 8 * ctiles);
-    take(&L.t_bytes, 8 * ctiles);
-    take(&L.t_pieces, 8 * ctiles);
-    take(&L.head, 32);
-    take(&L.M, 4 * (nbuf + 1));
-    take(&L.mt, 4 * btiles);
-    L.bytes = (at + 15u) & ~uint64_t(15);
+    host_launch::Carver c;
+    L.G = c.take(8 * (nbuf + 1));
+    L.bt = c.take(8 * btiles);
+    L.c_segs = c.take(8 * nconns);
+    L.c_bytes = c.take(8 * nconns);
+    L.c_pieces = c.take(8 * nconns);
+    L.t_segs = c.take(8 * ctiles);
+    L.t_bytes = c.take(8 * ctiles);
+    L.t_pieces = c.take(8 * ctiles);
+    L.head = c.take(32);
+    L.M = c.take(4 * (nbuf + 1));
+    L.mt = c.take(4 * btiles);
+    L.bytes = c.end();
     return L;
 }
 
@@ -443,34 +440,30 @@ int sccsum_tcp_tx_data(const sccsum_tcp_tx_opts* opts, const sccsum_tcp_snd* d_s
     if (rc != SCCSUM_OK) return rc;
 
     const Layout L = layout_of(nconns, nbuf);
-    uint8_t* const ws = static_cast<uint8_t*>(d_workspace);
-    const auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(ws + at); };
-    const auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(ws + at); };
+    const Workspace ws(d_workspace);
     const bool tso = (opts->flags & SCCSUM_TCP_TSO) != 0;
     // uint16_t(mtu - 40), as tcp.hh:1590 casts it
     const uint32_t seg_len = tso ? opts->max_packet_len - kHdrs : (opts->mtu - kHdrs) & 0xFFFFu;
-    const In I{reinterpret_cast<const uint4*>(d_snd), d_buf_src, d_buf_len, d_buf_first, u64(L.G), nconns,
+    const In I{reinterpret_cast<const uint4*>(d_snd), d_buf_src, d_buf_len, d_buf_first, ws.u64(L.G), nconns,
                static_cast<uint32_t>(nconns ? nbuf : 0), seg_len, opts->headroom, tso ? 1u : 0u};
-    const Ws W{u64(L.c_segs), u64(L.c_bytes), u64(L.c_pieces), u64(L.t_segs), u64(L.t_bytes), u64(L.t_pieces),
-               u64(L.head), u32(L.M)};
+    const Ws W{ws.u64(L.c_segs), ws.u64(L.c_bytes), ws.u64(L.c_pieces), ws.u64(L.t_segs), ws.u64(L.t_bytes),
+               ws.u64(L.t_pieces), ws.u64(L.head), ws.u32(L.M)};
     const dim3 block(kBlock), ctiles(static_cast<unsigned>(tiles_of(nconns, kTile)));
-    hipError_t e = hipSuccess;
+    Chain c{st};
     if (nconns != 0) {
-        e = scan_array<uint64_t>(st, LoadLen{d_buf_len}, I.nbuf, u64(L.bt), u64(L.G));
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = scan_array<uint32_t>(st, LoadMark{I}, I.nbuf, u32(L.mt), u32(L.M));
-        if (e != hipSuccess) return static_cast<int>(e);
-        e = launch_kernel(conn_count, ctiles, block, 0, st, I, W);
-        if (e != hipSuccess) return static_cast<int>(e);
+        c.e = scan_array<uint64_t>(st, LoadLen{d_buf_len}, I.nbuf, ws.u64(L.bt), ws.u64(L.G));
+        if (c.ok()) c.e = scan_array<uint32_t>(st, LoadMark{I}, I.nbuf, ws.u32(L.mt), ws.u32(L.M));
+        c.launch(conn_count, ctiles, block, 0, I, W);
     }
-    e = launch_kernel(conn_scan, dim3(1), block, 0, st, I, W, max_segs, max_out_bytes, d_seg_first, d_total);
-    if (e != hipSuccess || nconns == 0) return static_cast<int>(e);
-    e = launch_kernel(conn_place, ctiles, block, 0, st, I, W, reinterpret_cast<uint4*>(d_run));
-    if (e != hipSuccess || max_segs == 0) return static_cast<int>(e);
+    c.launch(conn_scan, dim3(1), block, 0, I, W, max_segs, max_out_bytes, d_seg_first, d_total);
+    if (nconns == 0) return c.rc();
+    c.launch(conn_place, ctiles, block, 0, I, W, reinterpret_cast<uint4*>(d_run));
+    if (max_segs == 0) return c.rc();
     const uint64_t blocks = std::min<uint64_t>(tiles_of(max_segs, kSegTile), kSegMaxBlocks);
     const Out O{d_off, d_len, reinterpret_cast<uint32_t*>(d_out), d_seg_first, reinterpret_cast<uint2*>(d_desc),
                 max_segs + nbuf};
-    return static_cast<int>(launch_kernel(seg_emit, dim3(static_cast<unsigned>(blocks)), dim3(kSegBlock), 0, st, I, W, O));
+    c.launch(seg_emit, dim3(static_cast<unsigned>(blocks)), dim3(kSegBlock), 0, I, W, O);
+    return c.rc();
 }
 
 }  // extern "C"

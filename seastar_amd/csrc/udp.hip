@@ -45,12 +45,13 @@
 namespace udp {
 
 using bucket_pass::pitch_of;
-using host_launch::launch_kernel;
+using host_launch::Chain;
+using host_launch::device_ok;
 using host_launch::misaligned;
 using host_launch::stream_ok;
+using host_launch::upload;
 using wire::be16_at;
 using wire::kIpHdrMin;
-using wire::kMaxDevices;
 using wire::pseudo_seed;
 using wire::status_passes;
 using wire::tiles_of;
@@ -386,19 +387,15 @@ int run_rx(const Decode& dec, uint32_t channels, uint8_t* d_class, uint32_t* d_f
     const uint32_t buckets = channels + 1u;
     uint4* const stash = static_cast<uint4*>(d_workspace);
     uint32_t* const ws = reinterpret_cast<uint32_t*>(stash + dec.n);
-    hipError_t e = hipSuccess;
-    if (ntiles) {
-        e = launch_kernel(count_kernel<Decode>, dim3(ntiles), dim3(kBlock), 0, st, dec, channels, d_class, stash, ws,
-                          pitch);
-        if (e != hipSuccess) return static_cast<int>(e);
+    Chain c{st};
+    if (ntiles) c.launch(count_kernel<Decode>, dim3(ntiles), dim3(kBlock), 0, dec, channels, d_class, stash, ws, pitch);
+    if (c.ok()) {
+        c.e = bucket_pass::scan_buckets<kBlock, kMaxBuckets>(st, ws, ntiles, pitch, buckets, d_first,
+                                                             ws + uint64_t(kMaxBuckets) * pitch);
     }
-    e = bucket_pass::scan_buckets<kBlock, kMaxBuckets>(st, ws, ntiles, pitch, buckets, d_first,
-                                                       ws + uint64_t(kMaxBuckets) * pitch);
-    if (e != hipSuccess || !ntiles) return static_cast<int>(e);
-    e = launch_kernel(scatter_kernel<Decode>, dim3(ntiles), dim3(kBlock), 0, st, dec, channels,
-                      static_cast<const uint4*>(stash), static_cast<const uint32_t*>(ws), pitch,
-                      static_cast<const uint32_t*>(d_first), O);
-    return static_cast<int>(e);
+    if (!ntiles) return c.rc();
+    c.launch(scatter_kernel<Decode>, dim3(ntiles), dim3(kBlock), 0, dec, channels, stash, ws, pitch, d_first, O);
+    return c.rc();
 }
 
 }  // namespace udp
@@ -417,30 +414,18 @@ int sccsum_udp_ports_create(int device, const uint16_t* ports, uint32_t channels
     if (!out) return SCCSUM_EINVAL;
     *out = nullptr;
     if (!ports_ok(ports, channels)) return SCCSUM_EINVAL;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess) return e == hipErrorNoDevice ? SCCSUM_ENODEV : static_cast<int>(e);
-    if (device < 0 || device >= ndev || device >= kMaxDevices) return SCCSUM_ENODEV;
-    sccsum_udp_ports* t = nullptr;
-    const int rc = new_ports(ports, channels, &t);
+    int rc = device_ok(device);
     if (rc != SCCSUM_OK) return rc;
-    int cur = 0;
-    e = hipGetDevice(&cur);
-    if (e == hipSuccess) e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        void* d = nullptr;
-        e = hipMalloc(&d, kPorts);
-        if (e == hipSuccess) {
-            t->d_table = static_cast<uint8_t*>(d);
-            e = hipMemcpy(d, t->table.data(), kPorts, hipMemcpyHostToDevice);
-        }
-        (void)hipSetDevice(cur);  // the caller's binding is put back
-    }
-    if (e != hipSuccess) {
-        if (t->d_table) (void)hipFree(t->d_table);
+    sccsum_udp_ports* t = nullptr;
+    rc = new_ports(ports, channels, &t);
+    if (rc != SCCSUM_OK) return rc;
+    void* d[1];
+    rc = upload(device, {{t->table.data(), kPorts}}, d);
+    if (rc != SCCSUM_OK) {
         delete t;
-        return static_cast<int>(e);
+        return rc;
     }
+    t->d_table = static_cast<uint8_t*>(d[0]);
     t->device = device;
     *out = t;
     return SCCSUM_OK;
@@ -448,7 +433,7 @@ int sccsum_udp_ports_create(int device, const uint16_t* ports, uint32_t channels
 
 int sccsum_udp_ports_destroy(sccsum_udp_ports* t) {
     if (!t) return SCCSUM_OK;
-    const hipError_t e = t->d_table ? hipFree(t->d_table) : hipSuccess;
+    const hipError_t e = host_launch::free_all({t->d_table});
     delete t;
     return static_cast<int>(e);
 }
@@ -548,7 +533,9 @@ int sccsum_udp_send(const sccsum_udp_opts* opts, void* d_bytes, uint64_t bytes_l
                  opts->src_host, opts->mtu, opts->flags};
     const SendOut O{d_l4_off, d_l4_len, d_sum_len, d_seed, d_proto, d_needs_csum, d_status};
     const uint64_t blocks = (n + kSendBlock - 1) / kSendBlock;
-    return static_cast<int>(launch_kernel(send_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kSendBlock), 0, st, S, O));
+    Chain c{st};
+    c.launch(send_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kSendBlock), 0, S, O);
+    return c.rc();
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 import torch
 
+import cpp_host
 from seastar_amd import batch, native
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -418,6 +419,8 @@ def test_python_wrapper_validation():
                         ("host", 1 << 32), ("netmask", -1), ("table", object())):
         with pytest.raises(ValueError, match=name):
             batch.arp_learn_check(b, **dict(ok, **{name: value}))
+    with pytest.raises(ValueError, match="^table: need an ArpTable$"):
+        batch.arp_learn_check(b, **dict(ok, table=object()))
     host_table = batch.ArpTable({1: 2}, device=None)
     with pytest.raises(ValueError, match="table"):
         batch.arp_learn_check(b, **dict(ok, table=host_table))  # a host-only table is on no device
@@ -544,41 +547,15 @@ def test_known_answer_frames():
     assert s["status"].tolist() == [native.ST_NOARP, 0, 0] and s["total"].tolist() == [1, 42, 1, 1, 0, 0]
 
 
-def _cpp_cmd(exe: str, with_library: bool, extra=()) -> list:
-    lib_dir = os.path.join(REPO, "seastar_amd", "lib")
-    link = ["-L", lib_dir, "-lsccsum", "-Wl,-rpath," + lib_dir] if with_library else []
-    return ["-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(REPO, "include"), *extra,
-            os.path.join(REPO, "tests", "cpp", "eth_host.cc"), "-o", exe, *link]
-
-
 def test_cpp_classes_on_the_host(tmp_path):
     """seastar::net::arp_table, eth_rx and eth_tx (tests/cpp/eth_host.cc): the
     table against a std::map, workspace() against the C calls, and every
     argument error of the three device calls."""
-    exe = str(tmp_path / "eth_host")
-    r = subprocess.run(["g++", "-O2", *_cpp_cmd(exe, True)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert not r.stderr.strip(), r.stderr  # warning-free
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "eth_host: OK" in r.stdout
+    cpp_host.build_and_run(tmp_path, "eth_host", "eth_host: OK")
 
 
 def test_cpp_classes_on_the_host_sanitized(tmp_path):
     """The same stand-alone program with eth.hip itself compiled in, its host
     side under AddressSanitizer + UndefinedBehaviorSanitizer (device code is
     not instrumented): the table's build and lookup and the argument checks."""
-    exe = str(tmp_path / "eth_host_san")
-    host_san = []
-    for f in ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"):
-        host_san += ["-Xarch_host", f]
-    stub = tmp_path / "strerror.cc"  # the one symbol the C++ header needs from the rest of the library
-    stub.write_text('extern "C" const char* sccsum_strerror(int) { return "error"; }\n')
-    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "--offload-arch=gfx950", *host_san,
-           *_cpp_cmd(exe, False, extra=[os.path.join(REPO, "seastar_amd", "csrc", "eth.hip"), str(stub)])]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp_path)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    assert "eth_host: OK" in r.stdout and "runtime error" not in r.stderr
+    cpp_host.build_and_run_sanitized(tmp_path, "eth_host", "eth.hip", "eth_host: OK")

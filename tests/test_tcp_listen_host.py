@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import cpp_host
 import tcp_listen_fast as fast
 import tcp_listen_model as lm
 import tcp_listen_traffic as tr
@@ -275,40 +276,14 @@ def test_python_wrapper_validation():
 
 # ---------------------------------------------------------------- the C++ class
 
-def _cpp_cmd(exe: str, with_library: bool, extra=()) -> list:
-    lib_dir = os.path.join(REPO, "seastar_amd", "lib")
-    link = ["-L", lib_dir, "-lsccsum", "-Wl,-rpath," + lib_dir] if with_library else []
-    return ["-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(REPO, "include"), *extra,
-            os.path.join(REPO, "tests", "cpp", "tcp_listen_host.cc"), "-o", exe, *link]
-
-
 def test_cpp_class_on_the_host(tmp_path):
     """seastar::net::tcp_listen (tests/cpp/tcp_listen_host.cc): workspace() and
     the argument errors of the call, through the class and directly."""
-    exe = str(tmp_path / "tcp_listen_host")
-    r = subprocess.run(["g++", "-O2", *_cpp_cmd(exe, True)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert not r.stderr.strip(), r.stderr  # warning-free
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "tcp_listen_host: OK" in r.stdout
+    cpp_host.build_and_run(tmp_path, "tcp_listen_host", "tcp_listen_host: OK")
 
 
 def test_cpp_class_on_the_host_sanitized(tmp_path):
     """The same stand-alone program with tcp_listen.hip itself compiled in, its
     host side under AddressSanitizer + UndefinedBehaviorSanitizer (device code
     is not instrumented): the workspace layout and the argument checks."""
-    exe = str(tmp_path / "tcp_listen_host_san")
-    host_san = []
-    for f in ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"):
-        host_san += ["-Xarch_host", f]
-    stub = tmp_path / "strerror.cc"  # the one symbol the C++ header needs from the rest of the library
-    stub.write_text('extern "C" const char* sccsum_strerror(int) { return "error"; }\n')
-    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "--offload-arch=gfx950", *host_san,
-           *_cpp_cmd(exe, False, extra=[os.path.join(REPO, "seastar_amd", "csrc", "tcp_listen.hip"), str(stub)])]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp_path)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    assert "tcp_listen_host: OK" in r.stdout and "runtime error" not in r.stderr
+    cpp_host.build_and_run_sanitized(tmp_path, "tcp_listen_host", "tcp_listen.hip", "tcp_listen_host: OK")

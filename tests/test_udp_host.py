@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import cpp_host
 import oracle
 import stack_model as sm
 import udp_model
@@ -176,6 +177,10 @@ def test_python_wrapper_validation():
                         ("cls", torch.zeros(n - 1, dtype=torch.uint8)), ("cls", torch.zeros(n, dtype=torch.int32))):
         with pytest.raises(ValueError, match=name):
             batch.udp_rx_check(b, **dict(ok, **{name: value}))
+    with pytest.raises(ValueError, match="^ports: need a UdpPorts$"):   # the wording is part of the interface
+        batch.udp_rx_check(b, **dict(ok, ports=object()))
+    with pytest.raises(ValueError, match="^ports: the table lives on None, the data on cpu$"):
+        batch.udp_rx_check(b, **dict(ok, ports=batch.UdpPorts((1,), device=None)))
     with pytest.raises(ValueError, match="PacketBatch"):
         batch.udp_rx_check(None, **ok)
     with pytest.raises(ValueError, match="ReasmResult"):
@@ -360,41 +365,15 @@ def test_fast_rx_is_the_model(nch):
 
 # ---------------------------------------------------------------- the C++ classes
 
-def _cpp_cmd(exe: str, with_library: bool, extra=()) -> list:
-    lib_dir = os.path.join(REPO, "seastar_amd", "lib")
-    link = ["-L", lib_dir, "-lsccsum", "-Wl,-rpath," + lib_dir] if with_library else []
-    return ["-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(REPO, "include"), *extra,
-            os.path.join(REPO, "tests", "cpp", "udp_host.cc"), "-o", exe, *link]
-
-
 def test_cpp_classes_on_the_host(tmp_path):
     """seastar::net::udp_ports, udp_rx and udp_tx (tests/cpp/udp_host.cc): the
     table against a std::map, workspace() and taken(), and every argument
     error of the three device calls."""
-    exe = str(tmp_path / "udp_host")
-    r = subprocess.run(["g++", "-O2", *_cpp_cmd(exe, True)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert not r.stderr.strip(), r.stderr  # warning-free
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "udp_host: OK" in r.stdout
+    cpp_host.build_and_run(tmp_path, "udp_host", "udp_host: OK")
 
 
 def test_cpp_classes_on_the_host_sanitized(tmp_path):
     """The same stand-alone program with udp.hip itself compiled in, its host
     side under AddressSanitizer + UndefinedBehaviorSanitizer (device code is
     not instrumented): the table's build and lookup and the argument checks."""
-    exe = str(tmp_path / "udp_host_san")
-    host_san = []
-    for f in ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"):
-        host_san += ["-Xarch_host", f]
-    stub = tmp_path / "strerror.cc"  # the one symbol the C++ header needs from the rest of the library
-    stub.write_text('extern "C" const char* sccsum_strerror(int) { return "error"; }\n')
-    cmd = ["/opt/rocm/bin/hipcc", "-O1", "-g", "--offload-arch=gfx950", *host_san,
-           *_cpp_cmd(exe, False, extra=[os.path.join(REPO, "seastar_amd", "csrc", "udp.hip"), str(stub)])]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp_path)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    assert "udp_host: OK" in r.stdout and "runtime error" not in r.stderr
+    cpp_host.build_and_run_sanitized(tmp_path, "udp_host", "udp.hip", "udp_host: OK")
